@@ -8,7 +8,9 @@ replicate indices (a Monte-Carlo sweep of the cell), so nothing is cached or ski
 Multi-GPU: one process per GPU, replicates sharded per rank (weak scaling: R per GPU
 per step), accumulators all-gathered once at the end (the only collective).
 
-Prints ONE JSON line (rank 0).
+A plain run sets up, warms up, times the steps and prints ONE JSON line (rank 0).  --full adds
+what takes runs of its own: the CPU baseline (before the GPU is touched) and the live pass
+ceilings (after the timed steps).  --dump-outputs DIR writes what the last timed step computed.
 """
 from __future__ import annotations
 
@@ -28,6 +30,7 @@ FP64_PEAK_TFLOPS = 78.6          # MI355X FP64 vector (spec); SURVEY §8d: 3.93e
 W_SAMPLE = {"gaussian": 260, "bernoulli": 120, "bounded_factor": 292}  # SURVEY §8d pinned weights
 W_BATCH = 183
 W_REP = 2.0e5
+DUMP_MAX_ROWS = 1_000_000        # --dump-outputs: at most this many record rows (48 B each) over all ranks
 
 
 def work_units(cell, m, k):
@@ -274,8 +277,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=8192, help="replicates per GPU per step")
     ap.add_argument("--n", type=int, default=100_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ceilings", action="store_true", help="skip the live pass ceilings (roofline.issue_frac)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline (cpu_baseline) and the live pass ceilings "
+                         "(roofline.issue_frac): measurements of their own, outside the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float64): records, the simulate() output [reps, 6]; accum_summary, that step's "
+                         "accumulators finalised [NI|INT, mse bias var coverage ci_length]; a rank of a "
+                         "multi-GPU run writes <name>_rank<r>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-ceilings", action="store_true",
+                    help="with --full: skip the live pass ceilings (roofline.issue_frac)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--variant", action="append", default=[], metavar="NAME=VALUE",
                     help="engine implementation switch for A/B runs (dcor_set_variant; repeatable)")
@@ -307,7 +319,7 @@ def main():
             sys.exit(3)
         return dry_run(world, rank)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:   # before the GPU is touched (the pool forks nothing)
+    if args.full and world == 1 and not args.no_cpu_baseline:   # before the GPU is touched (the pool forks nothing)
         from dcor.sim import headline_cell as _hc
         cpu = cpu_baseline(_hc(args.n), args.cpu_seconds)
     if world > 1:
@@ -376,6 +388,8 @@ def main():
     # would undercount; this span counts every call's kernels once and excludes only host time
     # before the first launch and after the last.
     kern_ms = ev[0][0].elapsed_time(ev[-1][1]) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, buf, host[-1], cell.rho, rank, world)
 
     total_reps = R * args.steps * world
     value = total_reps / el
@@ -386,7 +400,7 @@ def main():
     # live pass ceilings (after the timed region; untimed): the physical roofline of the VALU-bound path
     chunk, nch = sim_chunking(cell, R)       # the launch shape dcor_sim_launch used for R replicates
     passes = None
-    if rank == 0 and not args.no_ceilings and cell.n > 16384 and m == 8:
+    if args.full and rank == 0 and not args.no_ceilings and cell.n > 16384 and m == 8:
         passes = measure_passes(cell, chunk, rep_begin=(args.steps + args.warmup) * world * R)
     issue = None
     if passes:
@@ -469,6 +483,27 @@ def dry_run(world: int, rank: int) -> None:
                           "world_formed": formed, "merged_n": merged[0].n}), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(dirname, records, accum, rho, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: what a caller of the timed path holds after the last timed step -- the
+    simulate() records still in the step buffer and that step's accumulators (finalised: the
+    accumulator itself is a struct of counts and double-double sums) -- as float64 .npy files.  The
+    replicate indices of a step depend only on (step, rank, world, reps) and the cell's seed is
+    fixed, so the same arguments give the same arrays from run to run."""
+    import numpy as np
+
+    from dcor.sim import finalize
+    os.makedirs(dirname, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    cols = ("mse", "bias", "var", "coverage", "ci_length")
+    summ = np.array([[finalize(a, rho)[c] for c in cols] for a in accum], dtype=np.float64)
+    rec = records.cpu().numpy().astype(np.float64, copy=False)
+    cap = max(1, DUMP_MAX_ROWS // world)
+    if rec.shape[0] > cap:      # a fixed, seeded sample of rows (sorted) keeps all ranks' dumps under 64 MB
+        rec = rec[np.sort(np.random.default_rng(0).choice(rec.shape[0], cap, replace=False))]
+    np.save(os.path.join(dirname, f"records{tag}.npy"), rec)
+    np.save(os.path.join(dirname, f"accum_summary{tag}.npy"), summ)
 
 
 def merge_from(host, meth):

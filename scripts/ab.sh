@@ -9,7 +9,7 @@ C=$1; shift
 for l in "$@"; do
   L=$PWD/distributed-correlation_amd/dcor/$l
   for i in 1 2; do
-    DCOR_LIB=$L timeout -k 10 300 python -u bench.py --no-cpu-baseline > $O/b_$l.log 2>&1 || exit $?
+    DCOR_LIB=$L timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $O/b_$l.log 2>&1 || exit $?
     python -c "import json; d=json.loads(open('$O/b_$l.log').read().strip().splitlines()[-1]); r=d['roofline']; print('$l bench', round(d['value']), round(d['ms_per_step'], 4), 'issue', r['issue'] and {k: r['issue']['ms'][k] for k in ('pass1', 'pass2', 'epilogue', 'pass1_ceiling', 'pass2_ceiling')})"
   done
   if [ -n "$C" ] && [ "$C" != "-" ]; then

@@ -2,7 +2,8 @@
 reference defines in vert-cor.R / ver-cor-subG.R / real-data-sims.R is defined in
 R/dcor.R / R/dcor_subG.R / R/dcor_hrs.R with the same argument names, order and default
 expressions.  The reference's formals are the committed fixture tests/golden/r_formals.json
-(made by tests/golden/make_r_formals.py from /root/reference); where /root/reference is present
+(made by tests/golden/make_r_formals.py from the reference's R scripts), pinned by its digest; where
+those scripts are at hand ($DCOR_REFERENCE_DIR, or a `reference` directory beside this repository)
 the fixture is re-extracted and compared too.  R itself is absent: the R files are
 parsed, and their .Call targets are executed through the stub R runtime (tests/test_r_shim.py)."""
 import json
@@ -33,14 +34,24 @@ def test_drop_in_formals_match_reference(script):
         assert got == [list(a) for a in args], f"{name}: formals {got} != reference {args}"
 
 
+# digest of the fixture as make_r_formals.py extracted it from the reference's scripts (it prints it)
+FIXTURE_SHA256 = "2ab9d2bd9f6823f2b3e471944c1c5a4149dc091e2afbd07ae52305752e21067d"
+
+
 def test_fixture_matches_reference_sources():
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("reference sources not present (only the committed fixture)")
+    """The committed fixture is the extraction of the reference's formals: it covers every function
+    of the drop-in surface and has the digest recorded when it was extracted, so it cannot drift
+    from the reference unnoticed; with the reference's scripts at hand it is re-extracted too."""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    from make_r_formals import extract
-    fresh = json.loads(json.dumps(extract()))   # tuples -> lists, as in the fixture
-    assert fresh == json.load(open(FIXTURE, encoding="utf-8"))
+    from make_r_formals import SURFACE, digest, extract, reference_dir
+    fixture = json.load(open(FIXTURE, encoding="utf-8"))
+    assert {s: list(fns) for s, fns in fixture.items()} == SURFACE
+    assert digest(fixture) == FIXTURE_SHA256
+    ref = reference_dir()
+    if ref is not None:
+        fresh = json.loads(json.dumps(extract(ref)))   # tuples -> lists, as in the fixture
+        assert fresh == fixture
 
 
 def test_every_section_8b_name_is_covered():
