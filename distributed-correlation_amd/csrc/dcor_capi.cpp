@@ -520,8 +520,7 @@ int prepare_cell(const dcor_cell& c, CellPlan& p) {
   if (int st = make_dgp(c, g)) return st;
   p.dgp = c.dgp;
   p.nan_dgp = g.nan_dgp != 0;
-  const char* var = dcor::variant("DCOR_SIGN_KERNEL");
-  const bool force_regen = var && std::strcmp(var, "regen") == 0;
+  const bool force_regen = dcor::variant("DCOR_SIGN_KERNEL").is("regen");
   if (c.family == DCOR_FAMILY_SIGN) {
     SignConst& k = p.sign;
     if (int st = make_sign(c.n, c.eps1, c.eps2, c.alpha, c.normalise, c.ci_mode, c.nsim, false, k)) return st;
@@ -541,18 +540,16 @@ int prepare_cell(const dcor_cell& c, CellPlan& p) {
       // round-3 window, 2 sd of the sample around mu.
       const double sx = std::sqrt(g.a00 * g.a00 + g.a01 * g.a01);
       const double sy = std::sqrt(g.a10 * g.a10 + g.a11 * g.a11);
-      const char* wv = dcor::variant("DCOR_CODE_WINDOW");
-      if (wv && std::strcmp(wv, "wide") == 0) {
+      const Variant wv = dcor::variant("DCOR_CODE_WINDOW");
+      if (wv.is("wide")) {
         cx = r_min(r_max(c.mu[0], -k.L), k.L); cy = r_min(r_max(c.mu[1], -k.L), k.L);
         rx = 2.0 * sx;
         ry = 2.0 * sy;
       } else {
         // DCOR_CODE_WINDOW=<a>,<b> (A/B runs): a sd(mean) + b noise scales instead of 7, 24
         double wa = 7.0, wb = 24.0;
-        if (wv) {
-          double a2 = 0, b2 = 0;
-          if (std::sscanf(wv, "%lf,%lf", &a2, &b2) == 2 && a2 > 0 && b2 > 0) { wa = a2; wb = b2; }
-        }
+        double a2 = 0, b2 = 0;
+        if (wv.set() && std::sscanf(wv.str().c_str(), "%lf,%lf", &a2, &b2) == 2 && a2 > 0 && b2 > 0) { wa = a2; wb = b2; }
         const double rn = 1.0 / std::sqrt((double)c.n);
         cx = clipped_normal_mean(c.mu[0], sx, k.L);
         cy = clipped_normal_mean(c.mu[1], sy, k.L);
@@ -636,14 +633,11 @@ int variant_index(const char* name) {
 }
 }  // namespace
 
-const char* variant(const char* name) {
+Variant variant(const char* name) {
   const int i = variant_index(name);
-  if (i < 0) return nullptr;
-  thread_local std::string copy[kNVariants];
+  if (i < 0) return Variant();
   std::lock_guard<std::mutex> lk(g_var_mu);
-  if (!g_var_set[i]) return nullptr;
-  copy[i] = g_var_val[i];
-  return copy[i].c_str();
+  return g_var_set[i] ? Variant(g_var_val[i]) : Variant();
 }
 }  // namespace dcor
 
@@ -672,12 +666,12 @@ int dcor_get_variant(const char* name, char* buf, size_t len) {
     fail(DCOR_EINVAL, "unknown implementation switch %s", name ? name : "(null)");
     return -1;
   }
-  const char* v = dcor::variant(name);
+  const dcor::Variant v = dcor::variant(name);
   if (buf && len) {
-    std::strncpy(buf, v ? v : "", len - 1);
+    std::strncpy(buf, v.str().c_str(), len - 1);
     buf[len - 1] = 0;
   }
-  return v != nullptr;
+  return v.set();
 }
 
 int dcor_last_error(char* buf, size_t len) {
@@ -790,7 +784,7 @@ static void codes_chunking(int64_t n, int64_t rep_count, int64_t* chunk, int64_t
 int dcor_sim_launch(const dcor_cell* cell, int64_t rep_begin, int64_t rep_count,
                     dcor_rep_out* d_out, void* stream) {
   if (!cell || (rep_count > 0 && !d_out)) return fail(DCOR_EINVAL, "null argument");
-  if (rep_begin < 0 || rep_count < 0 || rep_begin + rep_count > 0xffffffffLL)
+  if (rep_begin < 0 || rep_count < 0 || rep_range_exceeds(rep_begin, rep_count))
     return fail(DCOR_EINVAL, "replicate range must lie in [0, 2^32)");
   if (rep_count > 0x7fffffffLL) return fail(DCOR_EINVAL, "rep_count too large for one launch");
   if (int st = need_device()) return st;
@@ -847,10 +841,9 @@ int dcor_sim_launch(const dcor_cell* cell, int64_t rep_begin, int64_t rep_count,
       }
       bf.lib[0] = bf.lib[1] = bf.ev_entry = bf.ev_end[0] = bf.ev_end[1] = nullptr;
       bf.cross = false;
-      const char* pv = dcor::variant("DCOR_SIGN_PIPELINE");
       Pipe* pp = nullptr;
       if (int st = pipe_get(&pp)) return st;
-      if (nbuf == 2 && !(pv && std::strcmp(pv, "0") == 0)) {
+      if (nbuf == 2 && !dcor::variant("DCOR_SIGN_PIPELINE").is("0")) {
         bf.lib[0] = pp->s2; bf.lib[1] = pp->s;
         bf.ev_entry = pp->entry; bf.ev_end[0] = pp->end[0]; bf.ev_end[1] = pp->end[1];
         // calls of the same layout back to back: the next call's first chunks may start while
@@ -858,8 +851,7 @@ int dcor_sim_launch(const dcor_cell* cell, int64_t rep_begin, int64_t rep_count,
         // caller's stream)
         const uint64_t sig = ((uint64_t)(uintptr_t)scratch * 1000003u) ^ ((uint64_t)slab_b * 31u) ^
                              ((uint64_t)sums_b << 1) ^ 1u;
-        const char* xv = dcor::variant("DCOR_SIGN_XCALL");
-        bf.cross = sig == prev_sig && !(xv && std::strcmp(xv, "0") == 0);
+        bf.cross = sig == prev_sig && !dcor::variant("DCOR_SIGN_XCALL").is("0");
         pp->sig = sig;
       } else {
         pp->sig = 0;
@@ -885,7 +877,7 @@ int dcor_sim_chunking(const dcor_cell* cell, int64_t rep_count, int64_t* chunk, 
 }
 
 int dcor_diag_sign_pass(const dcor_cell* cell, int64_t rep_begin, int64_t reps, int which, void* stream) {
-  if (!cell || reps < 1 || reps > 65535 || rep_begin < 0 || rep_begin + reps > 0xffffffffLL)
+  if (!cell || reps < 1 || reps > 65535 || rep_begin < 0 || rep_range_exceeds(rep_begin, reps))
     return fail(DCOR_EINVAL, "diag_sign_pass: bad arguments");
   if ((which < 1 || which > 3) && (which < 11 || which > 15))
     return fail(DCOR_EINVAL, "diag_sign_pass: which must be 1-3 or 11-15");
@@ -1015,37 +1007,119 @@ static int premat_subg_const(const dcor_premat_subg* d, PrematSubgConst& p) {
   return DCOR_OK;
 }
 
-}  // extern "C" (reopened below)
-
 struct dcor_panel {
   const double* X;
   const double* Y;
   int64_t n;
-  void* buf;          // codes (n u16, 256-B padded) | 512 dictionary doubles | ok flag
-  size_t codes_b;
+  void* buf;          // CodedPanelLayout(n)
+  dcor::CodedPanelLayout lay;
   void* stream;
   int coded;          // host copy of the device flag (read once at create)
-  uint16_t* codes() const { return (uint16_t*)buf; }
-  double* dict() const { return (double*)((char*)buf + codes_b); }
-  int* ok() const { return (int*)((char*)buf + codes_b + 512 * sizeof(double)); }
+  uint16_t* codes() const { return lay.codes(buf); }
+  double* dict() const { return lay.dict(buf); }
+  int* ok() const { return lay.ok(buf); }
 };
 
+// scratch / scratch_b: a caller's stream-ordered PrematScratchLayout buffer (the sweep's), used
+// when it is large enough
 static int premat_subg_run(const dcor_premat_subg* d, const dcor_panel* panel, dcor_rep_out* d_out,
-                           void* stream, void* scratch = nullptr, size_t scratch_b = 0);
+                           void* stream, void* scratch = nullptr, size_t scratch_b = 0) {
+  if (!d || !d_out || d->reps < 0) return fail(DCOR_EINVAL, "null argument");
+  if (!d->X || !d->Y || !d->lap_ni_x || !d->lap_ni_y || !d->lap_local || !d->lap_central ||
+      !d->mix_z || !d->mix_l)
+    return fail(DCOR_EINVAL, "premat_subg: every input array except perm is required");
+  if (int st = need_device()) return st;
+  PrematSubgConst p;
+  if (int st = premat_subg_const(d, p)) return st;
+  // stream-ordered scratch for the stream -> epilogue partials: safe under concurrent
+  // launches on different streams.
+  // HRS over one shared panel: the packed clipped panel (2 x n x 16 B) follows the partials.
+  // a prepared panel's path is known on the host: launch only the kernel that does the work
+  const bool pack = p.hrs && p.perm && p.xy_stride == 0 && !(panel != nullptr && panel->coded);
+  // Shared panel + random batches: try the dictionary-coded LDS kernel first (the device
+  // decides; the packed L2-gather kernel is the fallback).
+  const bool dict = p.perm && p.xy_stride == 0 && p.s.n <= DCOR_DICT_NMAX &&
+                    premat_dict_lds_bytes(p.s.n) <= (size_t)kLdsDynMax && panel == nullptr;
+  // partials: 80 B per replicate slice (a prepared coded panel slices each replicate)
+  const int64_t pslots = (panel != nullptr && panel->coded) ? DCOR_DICT_SLICES : 1;
+  const PrematScratchLayout lay(d->reps, pslots, p.s.n, pack, dict);
+  // a caller's stream-ordered scratch (the sweep's) when it is large enough: no per-launch
+  // pool allocation, whose cross-stream reuse would order one stream's launches after another's
+  const bool own = !(scratch != nullptr && scratch_b >= lay.bytes);
+  void* part = own ? nullptr : scratch;
+  if (own) {
+    if (hipMallocAsync(&part, lay.bytes, (hipStream_t)stream) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(DCOR_ENOMEM, "premat sub-G: cannot allocate %zu scratch bytes", lay.bytes);
+    }
+    count_alloc();
+  }
+  if (pack) { p.xyc = lay.xyc(part); p.soc = lay.soc(part); }
+  if (dict) {
+    void* q = lay.coded_base(part);
+    p.dict_codes = lay.coded.codes(q);
+    p.dict_vals = lay.coded.dict(q);
+    p.dict_ok = lay.coded.ok(q);
+  } else if (panel != nullptr && p.perm && panel->coded) {
+    p.dict_codes = panel->codes();
+    p.dict_vals = panel->dict();
+    p.dict_ok = panel->ok();
+    p.dict_built = 2;  // built and known coded: no L2-gather launch
+  }
+  int rc = 0;
+  if (panel != nullptr && panel->coded && p.perm && d->reps >= 4096 &&
+      dcor::variant("DCOR_PREMAT_PIPELINE").is("1")) {
+    // DCOR_PREMAT_PIPELINE=1: two replicate halves, the first half's mixquant epilogue on the
+    // auxiliary stream beside the second half's streaming kernel.  Off by default: the
+    // streaming kernel already reads at ~5.8 TB/s, and the epilogue's workgroups beside it
+    // cost more than they hide (r01 A/B: 12.5e6 piped vs 13.0e6 serial replicates/s).
+    Pipe* pp = nullptr;
+    if (int st = pipe_get(&pp)) {
+      if (own) (void)hipFreeAsync(part, (hipStream_t)stream);
+      return st;
+    }
+    const int64_t half = d->reps / 2;
+    for (int h = 0; h < 2 && !rc; ++h) {
+      const int64_t r0 = h ? half : 0, nr = h ? d->reps - half : half;
+      PrematSubgConst q = p;
+      const int64_t km = p.s.k * p.s.m, n = p.s.n, ns = p.s.mix.nsim;
+      q.perm = p.perm + r0 * km;
+      q.lap_ni_x = p.lap_ni_x + r0 * p.s.k;
+      q.lap_ni_y = p.lap_ni_y + r0 * p.s.k;
+      q.lap_local = p.lap_local + r0 * n;
+      q.lap_central = p.lap_central + r0;
+      q.mix_z = p.mix_z + r0 * ns;
+      q.mix_l = p.mix_l + r0 * ns;
+      PrematAux aux;   // the first half's epilogue on the auxiliary stream
+      if (h == 0) { aux.epi_stream = pp->s; aux.epi_event = pp->fork; }
+      rc = launch_premat_subg(q, nr, lay.partials(part, r0 * pslots), d_out + r0, stream, aux);
+    }
+    if (!rc && hipEventRecord(pp->join, pp->s) != hipSuccess) rc = (int)hipGetLastError();
+    if (!rc && hipStreamWaitEvent((hipStream_t)stream, pp->join, 0) != hipSuccess) rc = (int)hipGetLastError();
+  } else {
+    // the tiled path's INT kernel may run on the auxiliary stream (DCOR_TILED_INT=2)
+    Pipe* pp = nullptr;
+    PrematAux aux;
+    if (tiled_int_mode() == 2 && pipe_get(&pp) == 0) {
+      aux.int_stream = pp->s; aux.ev_fork = pp->fork; aux.ev_join = pp->join;
+    }
+    rc = launch_premat_subg(p, d->reps, part, d_out, stream, aux);
+  }
+  if (own) (void)hipFreeAsync(part, (hipStream_t)stream);
+  if (rc) return hip_fail((hipError_t)rc, "premat_subg launch");
+  return DCOR_OK;
+}
 
 // The Philox noise of HRS replicates materialised in HBM (the dcor_perm_launch /
 // dcor_draws_launch sites of the fused kernel's contract, all seven arrays from one
 // launch_hrs_noise), then the pre-materialised panel kernels: the pipeline of dcor.hrs.hrs_replicates(rng='philox', mode='premat'), natively.
-// hrs_noise_per: bytes of one replicate's noise; hrs_premat_chunks runs d->reps replicates in
-// chunks of cr over the caller's stream-ordered buffer of per * cr bytes.
-static size_t hrs_al(size_t b) { return (b + 255) & ~(size_t)255; }
-
+// hrs_noise_geometry's per: bytes of one replicate's noise; hrs_premat_chunks runs d->reps
+// replicates in chunks of cr over the caller's stream-ordered buffer of per * cr bytes.
 static int hrs_noise_geometry(const dcor_premat_subg* d, int64_t* k, int64_t* m, size_t* per) {
   int64_t km[2];
   if (int st = dcor_batch_geometry(d->n, d->eps1, d->eps2, DCOR_FAMILY_SUBG, 1, km)) return st;
   *k = km[0]; *m = km[1];
-  *per = hrs_al((size_t)km[0] * km[1] * 4) + 2 * hrs_al((size_t)km[0] * 8) +
-         hrs_al((size_t)d->n * 8) + 256 + 2 * hrs_al((size_t)d->nsim * 8);
+  *per = HrsNoiseLayout(d->n, km[0], km[1], d->nsim, 1).bytes;
   return DCOR_OK;
 }
 
@@ -1053,22 +1127,15 @@ static int hrs_premat_chunks(const dcor_premat_subg* d, const dcor_panel* panel,
                              uint64_t seed_int, int64_t rep_begin, dcor_rep_out* d_out, char* buf,
                              int64_t cr, int64_t k, int64_t m, void* stream,
                              void* scratch = nullptr, size_t scratch_b = 0) {
-  const int64_t n = d->n, ns = d->nsim;
-  int32_t* perm = (int32_t*)buf;
-  double* lx = (double*)(buf + hrs_al((size_t)cr * k * m * 4));
-  double* ly = lx + (hrs_al((size_t)cr * k * 8) / 8);
-  double* ll = ly + (hrs_al((size_t)cr * k * 8) / 8);
-  double* lc = ll + (hrs_al((size_t)cr * n * 8) / 8);
-  double* mz = lc + (hrs_al((size_t)cr * 8) / 8);
-  double* ml = mz + (hrs_al((size_t)cr * ns * 8) / 8);
+  HrsNoise j{seed_ni, seed_int, rep_begin, d->n, k, k * m, d->nsim};
+  HrsNoiseLayout(d->n, k, m, d->nsim, cr).point(buf, j);
+  dcor_premat_subg q = *d;
+  q.perm = j.perm; q.lap_ni_x = j.lap_x; q.lap_ni_y = j.lap_y; q.lap_local = j.lap_local;
+  q.lap_central = j.lap_central; q.mix_z = j.mix_z; q.mix_l = j.mix_l;
   for (int64_t r0 = 0; r0 < d->reps; r0 += cr) {
-    const int64_t nr = d->reps - r0 < cr ? d->reps - r0 : cr;
-    const HrsNoise j{seed_ni, seed_int, rep_begin + r0, n, k, k * m, ns, perm, lx, ly, ll, lc, mz, ml};
-    if (int rc = launch_hrs_noise(j, nr, stream)) return hip_fail((hipError_t)rc, "hrs noise launch");
-    dcor_premat_subg q = *d;
-    q.reps = nr;
-    q.perm = perm; q.lap_ni_x = lx; q.lap_ni_y = ly; q.lap_local = ll; q.lap_central = lc;
-    q.mix_z = mz; q.mix_l = ml;
+    q.reps = d->reps - r0 < cr ? d->reps - r0 : cr;
+    j.rep_begin = rep_begin + r0;
+    if (int rc = launch_hrs_noise(j, q.reps, stream)) return hip_fail((hipError_t)rc, "hrs noise launch");
     if (int e = premat_subg_run(&q, panel, d_out + r0, stream, scratch, scratch_b)) return e;
   }
   return DCOR_OK;
@@ -1106,8 +1173,6 @@ static int hrs_fused_materialised(const dcor_premat_subg* d, const dcor_panel* p
   return e;
 }
 
-extern "C" {
-
 int dcor_panel_create(const double* d_X, const double* d_Y, int64_t n, void* stream,
                       dcor_panel** out) {
   if (!d_X || !d_Y || !out || n < 1) return fail(DCOR_EINVAL, "panel_create: bad arguments");
@@ -1115,15 +1180,15 @@ int dcor_panel_create(const double* d_X, const double* d_Y, int64_t n, void* str
   *out = nullptr;
   dcor_panel* pn = new dcor_panel();
   pn->X = d_X; pn->Y = d_Y; pn->n = n; pn->stream = stream;
-  pn->codes_b = ((size_t)n * 2 + 255) & ~(size_t)255;
-  if (hipMalloc(&pn->buf, pn->codes_b + 512 * sizeof(double) + 256) != hipSuccess) {
+  pn->lay = CodedPanelLayout(n);
+  if (hipMalloc(&pn->buf, pn->lay.bytes) != hipSuccess) {
     (void)hipGetLastError();
     delete pn;
     return fail(DCOR_ENOMEM, "panel_create: cannot allocate the coded panel");
   }
   count_alloc();
   int rc = 0;
-  if (n <= DCOR_DICT_NMAX && premat_dict_lds_bytes(n) <= 150 * 1024)
+  if (n <= DCOR_DICT_NMAX && premat_dict_lds_bytes(n) <= (size_t)kLdsDynMax)
     rc = launch_panel_dict(d_X, d_Y, n, pn->codes(), pn->dict(), pn->ok(), stream);
   else
     rc = (int)hipMemsetAsync(pn->ok(), 0, sizeof(int), (hipStream_t)stream);
@@ -1172,18 +1237,14 @@ int dcor_hrs_fused_launch(const dcor_premat_subg* d, const dcor_panel* panel, ui
   if (d->X != panel->X || d->Y != panel->Y || d->xy_stride != 0 || d->n != panel->n)
     return fail(DCOR_EINVAL, "hrs_fused: X, Y, n must be the panel's and xy_stride 0");
   if (!d->hrs) return fail(DCOR_EINVAL, "hrs_fused: the HRS variant only (hrs = 1)");
-  if (rep_begin < 0 || rep_begin + d->reps > 0xffffffffLL)
+  if (rep_begin < 0 || rep_range_exceeds(rep_begin, d->reps))
     return fail(DCOR_EINVAL, "hrs_fused: replicate range exceeds 2^32");
   if (int st = need_device()) return st;
   PrematSubgConst p;
   if (int st = premat_subg_const(d, p)) return st;
   // DCOR_HRS_FUSED_L2=1 runs a coded panel through the uncoded kernel (A/B and the tests'
   // bit-identity check of the two kernels)
-  const bool force_l2 = [] {
-    const char* e = dcor::variant("DCOR_HRS_FUSED_L2");
-    return e && std::strcmp(e, "1") == 0;
-  }();
-  const bool coded = panel->coded && !force_l2;
+  const bool coded = panel->coded && !dcor::variant("DCOR_HRS_FUSED_L2").is("1");
   if (!coded && d->n > DCOR_DICT_NMAX)
     return hrs_fused_materialised(d, panel, seed_ni, seed_int, rep_begin, d_out, stream);
   p.perm = nullptr; p.lap_ni_x = p.lap_ni_y = p.lap_local = p.lap_central = nullptr;
@@ -1195,19 +1256,14 @@ int dcor_hrs_fused_launch(const dcor_premat_subg* d, const dcor_panel* panel, ui
     p.dict_codes = nullptr; p.dict_vals = nullptr; p.dict_ok = nullptr;
   }
   if (d->reps == 0) return DCOR_OK;
-  const size_t part_b = ((size_t)d->reps * 80 + 255) & ~(size_t)255;
-  const size_t pack_b = coded ? 0 : (size_t)d->n * 32;  // xyc | soc (uncoded kernel)
-  const size_t bytes = part_b + pack_b;
+  const PrematScratchLayout lay(d->reps, 1, d->n, !coded, false);  // pack: the uncoded kernel's
   void* part = nullptr;
-  if (hipMallocAsync(&part, bytes, (hipStream_t)stream) != hipSuccess) {
+  if (hipMallocAsync(&part, lay.bytes, (hipStream_t)stream) != hipSuccess) {
     (void)hipGetLastError();
-    return fail(DCOR_ENOMEM, "hrs_fused: cannot allocate %zu scratch bytes", bytes);
+    return fail(DCOR_ENOMEM, "hrs_fused: cannot allocate %zu scratch bytes", lay.bytes);
   }
   count_alloc();
-  if (!coded) {
-    p.xyc = (const double2*)((char*)part + part_b);
-    p.soc = p.xyc + d->n;
-  }
+  if (!coded) { p.xyc = lay.xyc(part); p.soc = lay.soc(part); }
   const int rc = launch_hrs_fused(p, seed_ni, seed_int, rep_begin, d->reps, part, d_out, stream);
   (void)hipFreeAsync(part, (hipStream_t)stream);
   if (rc) return hip_fail((hipError_t)rc, "hrs_fused launch");
@@ -1238,7 +1294,7 @@ int dcor_hrs_sweep_launch(const dcor_premat_subg* base, const dcor_panel* panel,
     if (g.reps < 0 || g.rep_begin < 0 || g.out_row < 0 || !(g.eps > 0.0))
       return fail(DCOR_EINVAL, "hrs_sweep: segment %lld: need eps > 0, reps, rep_begin, out_row >= 0",
                   (long long)i);
-    if (g.rep_begin + g.reps > 0xffffffffLL)
+    if (rep_range_exceeds(g.rep_begin, g.reps))
       return fail(DCOR_EINVAL, "hrs_sweep: segment %lld: replicate range exceeds 2^32", (long long)i);
     SegPlan& sp = plan[(size_t)i];
     dcor_premat_subg& q = sp.q;
@@ -1260,7 +1316,7 @@ int dcor_hrs_sweep_launch(const dcor_premat_subg* base, const dcor_panel* panel,
   // the premat launches' partials (80 B per replicate slice) and packed panel (uncoded: 32 B
   // per sample) follow the noise: one allocation per call, reused launch after launch in
   // stream order
-  const size_t scr_b = hrs_al((size_t)cap * 80 * DCOR_DICT_SLICES) + hrs_al((size_t)base->n * 32);
+  const size_t scr_b = al256(PrematScratchLayout(cap, DCOR_DICT_SLICES, base->n, true, false).bytes);
   char* buf = nullptr;
   const hipStream_t st = (hipStream_t)stream;
   if (hipMallocAsync((void**)&buf, need + scr_b, st) != hipSuccess) {
@@ -1280,114 +1336,16 @@ int dcor_hrs_sweep_launch(const dcor_premat_subg* base, const dcor_panel* panel,
   return e;
 }
 
-}  // extern "C" (reopened below)
-
-static int premat_subg_run(const dcor_premat_subg* d, const dcor_panel* panel, dcor_rep_out* d_out,
-                           void* stream, void* scratch, size_t scratch_b) {
-  if (!d || !d_out || d->reps < 0) return fail(DCOR_EINVAL, "null argument");
-  if (!d->X || !d->Y || !d->lap_ni_x || !d->lap_ni_y || !d->lap_local || !d->lap_central ||
-      !d->mix_z || !d->mix_l)
-    return fail(DCOR_EINVAL, "premat_subg: every input array except perm is required");
-  if (int st = need_device()) return st;
-  PrematSubgConst p;
-  if (int st = premat_subg_const(d, p)) return st;
-  // stream-ordered scratch for the stream -> epilogue partials: safe under concurrent
-  // launches on different streams.
-  // HRS over one shared panel: the packed clipped panel (2 x n x 16 B) follows the partials.
-  // a prepared panel's path is known on the host: launch only the kernel that does the work
-  const bool pack = p.hrs && p.perm && p.xy_stride == 0 && !(panel != nullptr && panel->coded);
-  // Shared panel + random batches: try the dictionary-coded LDS kernel first (the device
-  // decides; the packed L2-gather kernel is the fallback).
-  const bool dict = p.perm && p.xy_stride == 0 && p.s.n <= DCOR_DICT_NMAX &&
-                    premat_dict_lds_bytes(p.s.n) <= 150 * 1024 && panel == nullptr;
-  // partials: 80 B per replicate slice (a prepared coded panel slices each replicate)
-  const int64_t pslots = (panel != nullptr && panel->coded) ? DCOR_DICT_SLICES : 1;
-  const size_t part_b = ((size_t)d->reps * 80 * pslots + 255) & ~(size_t)255;
-  const size_t pack_b = pack ? (size_t)p.s.n * 32 : 0;
-  const size_t codes_b = dict ? (((size_t)p.s.n * 2 + 255) & ~(size_t)255) : 0;
-  const size_t dict_b = dict ? 2 * 256 * sizeof(double) + 256 : 0;
-  const size_t bytes = part_b + pack_b + codes_b + dict_b;
-  // a caller's stream-ordered scratch (the sweep's) when it is large enough: no per-launch
-  // pool allocation, whose cross-stream reuse would order one stream's launches after another's
-  const bool own = !(scratch != nullptr && scratch_b >= bytes);
-  void* part = own ? nullptr : scratch;
-  if (own) {
-    if (hipMallocAsync(&part, bytes, (hipStream_t)stream) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(DCOR_ENOMEM, "premat sub-G: cannot allocate %zu scratch bytes", bytes);
-    }
-    count_alloc();
-  }
-  if (pack) {
-    p.xyc = (const double2*)((char*)part + part_b);
-    p.soc = p.xyc + p.s.n;
-  }
-  if (dict) {
-    char* q = (char*)part + part_b + pack_b;
-    p.dict_codes = (uint16_t*)q;
-    p.dict_vals = (double*)(q + codes_b);
-    p.dict_ok = (int*)(q + codes_b + 2 * 256 * sizeof(double));
-  } else if (panel != nullptr && p.perm && panel->coded) {
-    p.dict_codes = panel->codes();
-    p.dict_vals = panel->dict();
-    p.dict_ok = panel->ok();
-    p.dict_built = 2;  // built and known coded: no L2-gather launch
-  }
-  int rc = 0;
-  const char* pv = dcor::variant("DCOR_PREMAT_PIPELINE");
-  if (panel != nullptr && panel->coded && p.perm && d->reps >= 4096 && pv && std::strcmp(pv, "1") == 0) {
-    // DCOR_PREMAT_PIPELINE=1: two replicate halves, the first half's mixquant epilogue on the
-    // auxiliary stream beside the second half's streaming kernel.  Off by default: the
-    // streaming kernel already reads at ~5.8 TB/s, and the epilogue's workgroups beside it
-    // cost more than they hide (r01 A/B: 12.5e6 piped vs 13.0e6 serial replicates/s).
-    Pipe* pp = nullptr;
-    if (int st = pipe_get(&pp)) {
-      if (own) (void)hipFreeAsync(part, (hipStream_t)stream);
-      return st;
-    }
-    const int64_t half = d->reps / 2;
-    for (int h = 0; h < 2 && !rc; ++h) {
-      const int64_t r0 = h ? half : 0, nr = h ? d->reps - half : half;
-      PrematSubgConst q = p;
-      const int64_t km = p.s.k * p.s.m, n = p.s.n, ns = p.s.mix.nsim;
-      q.perm = p.perm + r0 * km;
-      q.lap_ni_x = p.lap_ni_x + r0 * p.s.k;
-      q.lap_ni_y = p.lap_ni_y + r0 * p.s.k;
-      q.lap_local = p.lap_local + r0 * n;
-      q.lap_central = p.lap_central + r0;
-      q.mix_z = p.mix_z + r0 * ns;
-      q.mix_l = p.mix_l + r0 * ns;
-      rc = launch_premat_subg(q, nr, (char*)part + r0 * 80 * pslots, d_out + r0, stream, h ? nullptr : pp->s,
-                              pp->fork);
-    }
-    if (!rc && hipEventRecord(pp->join, pp->s) != hipSuccess) rc = (int)hipGetLastError();
-    if (!rc && hipStreamWaitEvent((hipStream_t)stream, pp->join, 0) != hipSuccess) rc = (int)hipGetLastError();
-  } else {
-    // the tiled path's INT kernel may run on the auxiliary stream (DCOR_TILED_INT=2)
-    Pipe* pp = nullptr;
-    const char* iv = dcor::variant("DCOR_TILED_INT");
-    if (iv && std::strcmp(iv, "2") == 0 && pipe_get(&pp) != 0) pp = nullptr;
-    rc = launch_premat_subg(p, d->reps, part, d_out, stream, nullptr, nullptr, pp ? pp->s : nullptr,
-                            pp ? pp->fork : nullptr, pp ? pp->join : nullptr);
-  }
-  if (own) (void)hipFreeAsync(part, (hipStream_t)stream);
-  if (rc) return hip_fail((hipError_t)rc, "premat_subg launch");
-  return DCOR_OK;
-}
-
-extern "C" {
-
 int dcor_panel_dict_probe(const double* d_X, const double* d_Y, int64_t n, int* ok) {
   if (!d_X || !d_Y || !ok || n < 1) return fail(DCOR_EINVAL, "panel_dict_probe: bad arguments");
   if (int st = need_device()) return st;
   *ok = 0;
   if (n > DCOR_DICT_NMAX) return DCOR_OK;
   DevBuf buf;
-  const size_t codes_b = ((size_t)n * 2 + 255) & ~(size_t)255;
-  HIPCHK(buf.alloc(codes_b + 512 * sizeof(double) + 256));
-  char* q = (char*)buf.p;
-  int* d_ok = (int*)(q + codes_b + 512 * sizeof(double));
-  const int rc = launch_panel_dict(d_X, d_Y, n, (uint16_t*)q, (double*)(q + codes_b), d_ok, nullptr);
+  const CodedPanelLayout lay(n);
+  HIPCHK(buf.alloc(lay.bytes));
+  int* d_ok = lay.ok(buf.p);
+  const int rc = launch_panel_dict(d_X, d_Y, n, lay.codes(buf.p), lay.dict(buf.p), d_ok, nullptr);
   if (rc) return hip_fail((hipError_t)rc, "panel_dict launch");
   HIPCHK(hipMemcpy(ok, d_ok, sizeof(int), hipMemcpyDeviceToHost));
   return DCOR_OK;
@@ -1491,8 +1449,8 @@ static int run_premat_subg_1(const double* X, const double* Y, int64_t n, double
   p.lap_ni_x = blx.as<double>(); p.lap_ni_y = bly.as<double>(); p.lap_local = bll.as<double>();
   p.lap_central = bc.as<double>(); p.mix_z = bmz.as<double>(); p.mix_l = bml.as<double>();
   DevBuf bpart;
-  HIPCHK(bpart.alloc(80));
-  const int rc = launch_premat_subg(p, 1, bpart.p, bout.as<dcor_rep_out>(), nullptr);
+  HIPCHK(bpart.alloc(sizeof(SubgPartial)));
+  const int rc = launch_premat_subg(p, 1, bpart.p, bout.as<dcor_rep_out>(), nullptr, PrematAux());
   if (rc) return hip_fail((hipError_t)rc, "premat_subg launch");
   HIPCHK(hipMemcpy(res, bout.p, sizeof(dcor_rep_out), hipMemcpyDeviceToHost));
   return DCOR_OK;
@@ -1584,7 +1542,7 @@ int dcor_perm_launch(uint64_t seed, int site, int64_t rep_begin, int64_t reps, i
   if (n < 1 || n > 0x7fffffffLL || count < 0 || count > n || reps < 0 || reps > 65535 ||
       (reps * count > 0 && !d_out))
     return fail(DCOR_EINVAL, "bad perm arguments (need 0 <= count <= n < 2^31, reps <= 65535)");
-  if (rep_begin < 0 || rep_begin + reps > 0xffffffffLL) return fail(DCOR_EINVAL, "rep range");
+  if (rep_begin < 0 || rep_range_exceeds(rep_begin, reps)) return fail(DCOR_EINVAL, "rep range");
   if (int st = need_device()) return st;
   const int rc = launch_perm((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)site, rep_begin,
                              reps, n, count, d_out, stream);
@@ -1625,7 +1583,7 @@ int dcor_dgp_launch(const dcor_cell* cell, int64_t rep_begin, int64_t reps, doub
   if (!cell || reps < 0 || cell->n < 1 || cell->n > 0x7fffffffLL || (reps > 0 && (!d_X || !d_Y)))
     return fail(DCOR_EINVAL, "bad dgp arguments");
   if (reps > 65535) return fail(DCOR_EINVAL, "dgp: at most 65535 replicates per launch");
-  if (rep_begin < 0 || rep_begin + reps > 0xffffffffLL) return fail(DCOR_EINVAL, "dgp: replicate range exceeds 2^32");
+  if (rep_begin < 0 || rep_range_exceeds(rep_begin, reps)) return fail(DCOR_EINVAL, "dgp: replicate range exceeds 2^32");
   DgpConst g;
   if (int st = make_dgp(*cell, g)) return st;
   if (int st = need_device()) return st;
@@ -1640,7 +1598,7 @@ int dcor_draws_launch(int kind, uint64_t seed, int site, int64_t rep_begin, int6
   if (kind < 0 || kind > 2 || reps < 0 || count < 0 || (reps * count > 0 && !d_out))
     return fail(DCOR_EINVAL, "bad draws arguments");
   if (reps > 65535) return fail(DCOR_EINVAL, "draws: at most 65535 replicates per launch");
-  if (rep_begin < 0 || rep_begin + reps > 0xffffffffLL || count > 0x7fffffffLL)
+  if (rep_begin < 0 || rep_range_exceeds(rep_begin, reps) || count > 0x7fffffffLL)
     return fail(DCOR_EINVAL, "draws: need rep_begin + reps <= 2^32 and count < 2^31");
   if (int st = need_device()) return st;
   const int rc = launch_draws(kind, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)site,
@@ -1810,7 +1768,7 @@ int rs_plan(const dcor_cell& cell, RsPlan& p) {
   p.rep_max = pre + shuffle_words + (c.has_mix ? 18 * c.nsim : 0);
   c.jpost = c.has_mix ? c.nsim : 0;
   p.jrep = pre + (c.has_mix ? c.nsim + 2 * c.nsim + 64 + 8 * (int64_t)std::ceil(std::sqrt((double)c.nsim)) : 0);
-  if (dcor::variant("DCOR_RSJ_TIGHT"))   // test hook: a budget every mixquant chunk overruns
+  if (dcor::variant("DCOR_RSJ_TIGHT").set())   // test hook: a budget every mixquant chunk overruns
     p.jrep = pre + (c.has_mix ? c.nsim + c.nsim : 0);
   p.rep_max = std::max(p.rep_max, p.jrep);
   const int64_t fw = (n + 31) / 32;
@@ -1819,8 +1777,6 @@ int rs_plan(const dcor_cell& cell, RsPlan& p) {
               (c.shuffle ? (size_t)n * 4 + 8 : 0) + sizeof(dcor_rep_out) + 256;
   return DCOR_OK;
 }
-
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // Carve cell c's buffers for rc replicates out of `base` (advanced).
 void rs_carve(RsPlan& p, int32_t rc, char*& base) {
@@ -1906,14 +1862,12 @@ size_t rsj_cell_bytes(const RsPlan& p) {
 bool rsj_use(const std::vector<RsPlan>& plan, int i0, int nb) {
   for (int i = 0; i < nb; ++i)
     if (plan[(size_t)(i0 + i)].c.shuffle) return false;
-  const char* e = dcor::variant("DCOR_RS_JUMP");
-  if (e && *e) return std::atoi(e) != 0;
-  return nb <= 64;
+  const Variant v = dcor::variant("DCOR_RS_JUMP");
+  return v.str().empty() ? nb <= 64 : v.as_int(0) != 0;
 }
 
 size_t rs_budget() {
-  const char* e = dcor::variant("DCOR_RS_BUDGET_MB");
-  const long mb = e ? std::atol(e) : 4096;
+  const long long mb = dcor::variant("DCOR_RS_BUDGET_MB").as_int(4096);
   return (size_t)(mb > 16 ? mb : 16) << 20;
 }
 
@@ -1943,8 +1897,8 @@ int dcor_rstream_grid_run(const dcor_cell* cells, int ncells, int64_t B, dcor_ac
     }
     int64_t rc = (int64_t)(budget / std::max<size_t>(sum, 1));
     rc = std::max<int64_t>(1, std::min<int64_t>({rc, B, (int64_t)(0x7fffffff / nb)}));
-    if (const char* e = dcor::variant("DCOR_RS_MAX_CHUNK"))   // test hook: force short chunks
-      rc = std::max<int64_t>(1, std::min<int64_t>(rc, std::atol(e)));
+    if (const Variant v = dcor::variant("DCOR_RS_MAX_CHUNK"); v.set())   // test hook: force short chunks
+      rc = std::max<int64_t>(1, std::min<int64_t>(rc, v.as_int(0)));
     bool jump = rsj_use(plan, i0, nb);
     size_t bytes = 0, jbytes = 0;
     for (;;) {

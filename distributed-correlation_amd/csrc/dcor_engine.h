@@ -7,13 +7,50 @@
 #pragma once
 #include <stdint.h>
 
+#include <climits>
+#include <cstdlib>
+#include <string>
+#include <utility>
+
 #include "../../include/dcor.h"
 
 namespace dcor {
 
-// The current value of an implementation switch set by dcor_set_variant (dcor_capi.cpp), or
-// nullptr when it is at its default.  Never the environment: see include/dcor.h.
-const char* variant(const char* name);
+// The value of an implementation switch at the time of the read: an owned copy, so a later
+// dcor_set_variant (any thread) cannot change or free what a reader holds.  The accessors are the
+// switches' parsers: text that does not parse, or parses outside [lo, hi], gives the default.
+class Variant {
+  std::string v_;
+  bool set_ = false;
+
+ public:
+  Variant() = default;
+  explicit Variant(std::string v) : v_(std::move(v)), set_(true) {}
+  bool set() const { return set_; }
+  bool is(const char* s) const { return set_ && v_ == s; }
+  const std::string& str() const { return v_; }   // empty when not set
+  long long as_int(long long dflt, long long lo = LLONG_MIN, long long hi = LLONG_MAX) const {
+    const long long x = set_ ? std::atoll(v_.c_str()) : dflt;
+    return (x >= lo && x <= hi) ? x : dflt;
+  }
+  // a positive count scaled by 2^shift (MB switches: 20), else the default
+  size_t as_size(size_t dflt, int shift) const {
+    const long long x = as_int(0);
+    return x > 0 ? (size_t)x << shift : dflt;
+  }
+};
+// The current value of an implementation switch set by dcor_set_variant (dcor_capi.cpp); not set
+// when it is at its default.  Never the environment: see include/dcor.h.
+Variant variant(const char* name);
+
+// Dynamic LDS a workgroup may ask for (hipFuncAttributeMaxDynamicSharedMemorySize) of the CU's
+// 160 KB: 150 KB for the persistent panel and R-stream kernels (the rest is left to static LDS),
+// all of it for the 1024-thread tiled kernel.
+constexpr int kLdsDynMax = 150 * 1024;
+constexpr int kLdsTiledMax = 160 * 1024;
+
+// Every scratch region on the panel / HRS path starts on a 256-B boundary.
+inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct DgpConst {
   int32_t dgp;
@@ -120,6 +157,42 @@ struct PrematSubgConst {
 // best -- 2 slices even out a persistent grid's last round but cost 25 % in per-item start-up
 // and reduction (r01 A/B: 590-605 us vs 735-760 us per 8192 replicates).
 #define DCOR_DICT_SLICES 1
+// A streaming kernel's sums of one replicate (slice) on their way to the epilogue.
+struct SubgPartial { double s[10]; };  // sP, sT, sT2, sU, sU2 as (hi, lo)
+static_assert(sizeof(SubgPartial) == 80, "scratch sizes and the kernels' partial stride");
+
+// ---- scratch layouts of the panel / HRS path: each the single definition of its buffer ----
+// Offsets and the total from the geometry, pointers over a base address.  Every region starts
+// 256-B aligned when the base is.
+// Coded panel: codes (n u16) | dict (2 columns x 256 doubles) | ok (one int in a 256-B tail).
+struct CodedPanelLayout {
+  size_t dict_off = 0, ok_off = 0, bytes = 0;
+  CodedPanelLayout() = default;
+  explicit CodedPanelLayout(int64_t n)
+      : dict_off(al256((size_t)n * 2)), ok_off(dict_off + 2 * 256 * sizeof(double)), bytes(ok_off + 256) {}
+  uint16_t* codes(void* base) const { return (uint16_t*)base; }
+  double* dict(void* base) const { return (double*)((char*)base + dict_off); }
+  int* ok(void* base) const { return (int*)((char*)base + ok_off); }
+};
+// Premat sub-G scratch: partials (one SubgPartial per replicate slice) | pack (xyc | soc: two
+// double2 per sample, uncoded shared panel) | a coded panel built per launch (dict).
+struct PrematScratchLayout {
+  int64_t n = 0;
+  size_t pack_off = 0, coded_off = 0, bytes = 0;
+  CodedPanelLayout coded;
+  PrematScratchLayout(int64_t reps, int64_t slices, int64_t n_, bool pack, bool dict)
+      : n(n_), pack_off(al256((size_t)reps * sizeof(SubgPartial) * slices)),
+        coded_off(pack_off + (pack ? (size_t)n_ * 2 * sizeof(double2) : 0)),
+        coded(dict ? CodedPanelLayout(n_) : CodedPanelLayout()) {
+    bytes = coded_off + coded.bytes;
+  }
+  // the partials from replicate slice `item` on
+  void* partials(void* base, int64_t item = 0) const { return (SubgPartial*)base + item; }
+  double2* xyc(void* base) const { return (double2*)((char*)base + pack_off); }
+  double2* soc(void* base) const { return xyc(base) + n; }
+  void* coded_base(void* base) const { return (char*)base + coded_off; }
+};
+
 size_t premat_dict_lds_bytes(int64_t n);
 // codes: n u16 (16-B padded), dict: 512 doubles, ok: 1 int (device).
 int launch_panel_dict(const double* X, const double* Y, int64_t n, uint16_t* codes, double* dict,
@@ -241,19 +314,25 @@ int launch_accumulate_pass(const dcor_rep_out* rec, const AccEntry* ent, int nen
 int launch_accumulate_merge_cells(const AccCell* cells, int ncells, const dcor_accum* part,
                                   dcor_accum* acc, void* stream);
 int launch_premat_sign(const PrematSignConst& c, int64_t reps, dcor_rep_out* out, void* stream);
-// part: reps * 80 B scratch (stream -> epilogue partial sums).
-// epi_stream / ev: if non-null the epilogue runs on epi_stream after an event recorded on
-// `stream` behind the streaming kernels (chunk pipelining).
 // HRS replicates [rep_begin, rep_begin + reps) with in-kernel Philox noise over a coded panel
 // (c.dict_codes / c.dict_vals set), or over an uncoded one (c.xyc / c.soc: 2 x n double2 of
 // scratch the launch packs; n <= DCOR_DICT_NMAX); part: reps * 80 B.
 int launch_hrs_fused(const PrematSubgConst& c, uint64_t seed_ni, uint64_t seed_int,
                      int64_t rep_begin, int64_t reps, void* part, dcor_rep_out* out, void* stream);
-// int_stream / ev_fork / ev_join: an auxiliary stream and two events for the tiled path's INT kernel
-// (DCOR_TILED_INT=2); without them that mode runs the INT sums inside the tiled kernel.
+// The auxiliary streams and events a premat sub-G launch may use; default: none.
+struct PrematAux {
+  // if non-null the epilogue runs on epi_stream after epi_event, recorded on `stream` behind the
+  // streaming kernels (chunk pipelining)
+  void* epi_stream = nullptr; void* epi_event = nullptr;
+  // an auxiliary stream and two events for the tiled path's INT kernel (DCOR_TILED_INT=2);
+  // without them that mode runs the INT sums inside the tiled kernel
+  void* int_stream = nullptr; void* ev_fork = nullptr; void* ev_join = nullptr;
+};
+// Where the tiled path's INT sums run (DCOR_TILED_INT, dcor_premat.hip): 0, 1 (default) or 2.
+int tiled_int_mode();
+// part: reps * 80 B scratch (stream -> epilogue partial sums).
 int launch_premat_subg(const PrematSubgConst& c, int64_t reps, void* part, dcor_rep_out* out,
-                       void* stream, void* epi_stream = nullptr, void* ev = nullptr,
-                       void* int_stream = nullptr, void* ev_fork = nullptr, void* ev_join = nullptr);
+                       void* stream, const PrematAux& aux = PrematAux());
 int launch_accumulate(const dcor_rep_out* d_out, int64_t count, double rho, dcor_accum* acc,
                       void* stream);
 int launch_mixquant(const double* z, const double* l, int32_t nsim, double c, int32_t pos,
@@ -274,6 +353,23 @@ struct HrsNoise {
   double *lap_x, *lap_y, *lap_local, *lap_central, *mix_z, *mix_l;
 };
 int launch_hrs_noise(const HrsNoise& j, int64_t reps, void* stream);
+// The seven arrays of cr replicates in one buffer: perm [cr][k m] i32 | lap_x, lap_y [cr][k] |
+// lap_local [cr][n] | lap_central [cr] | mix_z, mix_l [cr][nsim].  cr = 1 gives the bytes per
+// replicate a buffer is sized by; a chunk's layout fits cr times that.
+struct HrsNoiseLayout {
+  size_t off[7], bytes = 0;
+  HrsNoiseLayout(int64_t n, int64_t k, int64_t m, int64_t nsim, int64_t cr) {
+    const size_t b[7] = {(size_t)cr * k * m * 4, (size_t)cr * k * 8, (size_t)cr * k * 8,
+                         (size_t)cr * n * 8,     (size_t)cr * 8,     (size_t)cr * nsim * 8,
+                         (size_t)cr * nsim * 8};
+    for (int i = 0; i < 7; ++i) { off[i] = bytes; bytes += al256(b[i]); }
+  }
+  void point(char* base, HrsNoise& j) const {   // j's seven pointers over `base`
+    j.perm = (int32_t*)(base + off[0]);
+    double** const d[6] = {&j.lap_x, &j.lap_y, &j.lap_local, &j.lap_central, &j.mix_z, &j.mix_l};
+    for (int i = 0; i < 6; ++i) *d[i] = (double*)(base + off[i + 1]);
+  }
+};
 int launch_dp_sd(const double* x, int64_t n, double lo, double hi, double s_mu, double s_m2,
                  const double* lap2, double* out2, void* stream);
 // R-surface transforms (dcor_premat.hip): the arithmetic half of the R wrappers' DGPs and DP

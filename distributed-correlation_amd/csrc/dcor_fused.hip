@@ -1455,10 +1455,7 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_sign_epilogue(SignConst c,
 
 static inline void launch_sign_epilogue(const SignConst& c, int64_t nr, const SignPartial* part,
                                         dcor_rep_out* out, hipStream_t st) {
-  const int block_epi = [] {
-    const char* v = dcor::variant("DCOR_EPILOGUE");
-    return v && std::strcmp(v, "block") == 0;
-  }();
+  const bool block_epi = dcor::variant("DCOR_EPILOGUE").is("block");
   const unsigned gw = (unsigned)((nr + DCOR_WAVES - 1) / DCOR_WAVES);
   if (block_epi)
     hipLaunchKernelGGL(k_sign_epilogue, dim3((unsigned)nr), dim3(DCOR_BLOCK), 0, st, c, part, out);
@@ -2165,13 +2162,7 @@ static inline unsigned persistent_groups(int64_t nitems) {
 // Small cells: pass 2 and the epilogue fused into one wave kernel (default; VG 3.35e7 vs 3.25e7
 // replicates/s with the two kernels, r03c), or DCOR_SIGN_P2E=0 for the pass-2 wave kernel + the
 // wave epilogue kernel.
-static bool p2e_fused() {
-  const bool v = [] {
-    const char* e = dcor::variant("DCOR_SIGN_P2E");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  return v;
-}
+static bool p2e_fused() { return !dcor::variant("DCOR_SIGN_P2E").is("0"); }
 
 template <int DGP>
 static void grid_codes_w_t(const SignConst* cells, const GridItem* items, int64_t nitems, uint32_t* scratch,

@@ -39,14 +39,6 @@ using namespace dcor::host;
 
 namespace {
 
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-size_t env_size(const char* name, size_t dflt, int shift) {
-  const char* e = dcor::variant(name);
-  const long long v = e ? std::atoll(e) : 0;
-  return v > 0 ? (size_t)v << shift : dflt;
-}
-
 bool codes_kind(int kind) { return kind == GK_SIGN_CODES || kind == GK_SIGN_CODES_W; }
 bool subg_kind(int kind) { return kind == GK_SUBG || kind == GK_SUBG_W; }
 
@@ -92,10 +84,10 @@ int exec_ranges(const dcor_cell* cells, const std::vector<CellPlan>& cp, const s
   // longest first inside every launch: the big replicates start early, the small ones fill in
   std::stable_sort(order.begin(), order.end(),
                    [&](int a, int b) { return cells[ranges[a].cell].n > cells[ranges[b].cell].n; });
-  const size_t item_cap = env_size("DCOR_GRID_CHUNK_ITEMS", (size_t)1 << 19, 0);
+  const size_t item_cap = dcor::variant("DCOR_GRID_CHUNK_ITEMS").as_size((size_t)1 << 19, 0);
   int64_t max_n = 1;
   for (const Range& r : ranges) max_n = std::max<int64_t>(max_n, cells[r.cell].n);
-  size_t budget = env_size("DCOR_GRID_SLAB_MB", (size_t)1 << 30, 20);
+  size_t budget = dcor::variant("DCOR_GRID_SLAB_MB").as_size((size_t)1 << 30, 20);
   budget = std::max(budget, (size_t)1024 * (size_t)max_n * 4);
   budget = std::min(budget, (size_t)8 << 30);
   const uint64_t budget_el = budget / 4;   // u32 elements (u64 plane words count twice)
@@ -108,7 +100,7 @@ int exec_ranges(const dcor_cell* cells, const std::vector<CellPlan>& cp, const s
   // streams -- at the reference grids' n (1000-12000) pass 2 costs as much as pass 1
   struct Lim { uint64_t items = 0, scratch = 0, cap_items = 0, cap_scr = 0; };
   std::map<std::tuple<int, int, int>, Lim> lim;
-  const uint64_t min_chunks = env_size("DCOR_GRID_MIN_CHUNKS", 4, 0);
+  const uint64_t min_chunks = dcor::variant("DCOR_GRID_MIN_CHUNKS").as_size(4, 0);
   for (const Range& r : ranges) {
     const CellPlan& p = cp[(size_t)r.cell];
     if (r.count == 0 || p.nan_dgp) continue;
@@ -221,8 +213,7 @@ int exec_ranges(const dcor_cell* cells, const std::vector<CellPlan>& cp, const s
   const size_t extra_off = tb;
   tb += al256(extra_b);
   tb = std::max<size_t>(tb, 256);
-  const bool two = ncodes_chunks > 1 && !(dcor::variant("DCOR_SIGN_PIPELINE") &&
-                                         std::strcmp(dcor::variant("DCOR_SIGN_PIPELINE"), "0") == 0);
+  const bool two = ncodes_chunks > 1 && !dcor::variant("DCOR_SIGN_PIPELINE").is("0");
   const int nslot = two ? 2 : 1;
   const size_t sums_one = al256(std::max<size_t>(max_sums_b, 8));
   const size_t items_off = al256(tb), sums_off = items_off + al256(std::max<uint64_t>(tot_items, 1) * sizeof(GridItem));
@@ -345,7 +336,7 @@ int dcor_grid_launch(const dcor_cell* cells, int ncells, const int64_t* rep_begi
   int64_t tot = 0;
   for (int i = 0; i < ncells; ++i) {
     const int64_t b = rep_begin[i], c = rep_count[i];
-    if (b < 0 || c < 0 || b + c > 0xffffffffLL)
+    if (b < 0 || c < 0 || rep_range_exceeds(b, c))
       return fail(DCOR_EINVAL, "grid_launch: cell %d: replicate range must lie in [0, 2^32)", i);
     tot += c;
   }
@@ -416,7 +407,7 @@ int run_shard(const dcor_cell* cells, int ncells, int64_t B, dcor_rep_out* h_det
   const size_t np = partial_layout(counts.data(), ncells, poff, multi);
   const int64_t per = accumulate_per(nb), nblk = accumulate_blocks(nb);
   const int64_t pass_rec = std::max<int64_t>(
-      per, (int64_t)(env_size("DCOR_GRID_REC_MB", (size_t)256 << 20, 20) / sizeof(dcor_rep_out)));
+      per, (int64_t)(dcor::variant("DCOR_GRID_REC_MB").as_size((size_t)256 << 20, 20) / sizeof(dcor_rep_out)));
   const int64_t total = (int64_t)ncells * nb;
   const int64_t buf_rec = std::max<int64_t>(1, std::min<int64_t>(total, pass_rec));
   void* buf = nullptr;

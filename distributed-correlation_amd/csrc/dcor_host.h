@@ -26,6 +26,10 @@ int hip_fail(hipError_t e, const char* what);
 
 // DCOR_EFORK in a process forked after its parent used the engine, DCOR_ENODEV without a GPU.
 int need_device();
+// Replicate indices are 32-bit Philox counters: for rep_begin >= 0 and reps >= 0 (the caller
+// checks), true when rep_begin + reps > 2^32 - 1 -- without forming the sum, which overflows for
+// a huge rep_begin.
+inline bool rep_range_exceeds(int64_t rep_begin, int64_t reps) { return rep_begin > 0xffffffffLL - reps; }
 double r_min(double a, double b);
 double r_max(double a, double b);
 

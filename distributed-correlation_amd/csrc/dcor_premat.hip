@@ -127,8 +127,7 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_premat_sign(PrematSignConst p, d
 // Streaming kernel (one workgroup per replicate): NI batch means + INT clipped products,
 // compensated partial sums -> SubgPartial.  The mixquant / CI epilogue is a second kernel,
 // so the streaming kernel carries no sort scratch and keeps many loads in flight (each
-// thread issues UNR iterations' loads before using them).
-struct SubgPartial { double s[10]; };  // sP, sT, sT2, sU, sU2 as (hi, lo)
+// thread issues UNR iterations' loads before using them).  SubgPartial: dcor_engine.h.
 
 #define SUBG_UNR 4
 
@@ -774,6 +773,7 @@ __global__ __launch_bounds__(NT, WPE) void k_premat_subg_tiled(PrematSubgConst p
                                                               const int* __restrict__ dict_ok,
                                                               int64_t reps, int64_t tile_pairs_,
                                                               SubgPartial* __restrict__ part) {
+  static_assert(ENQ >= 0 && ENQ <= NQ, "the early noise loads are a prefix of the round's NQ");
   constexpr int NW = NT / 64;
   extern __shared__ double dsm[];
   if (dict_ok != nullptr && *dict_ok != 0) return;  // the coded kernel owns this launch
@@ -882,6 +882,7 @@ __global__ __launch_bounds__(NT, WPE) void k_premat_subg_tiled(PrematSubgConst p
         nx[u] = ld_nz(x_row, qc);
         ny[u] = ld_nz(y_row, qc);
       };
+      // at least one tile (the launcher passes tile_pairs >= 1): the loop fills nx / ny [0, ENQ)
       for (uint32_t ti = 0; ti < ntiles; ++ti) {
         // NI-only kernel: every other round sweeps the tiles in reverse, so it starts on the tile
         // the previous round (of this replicate or the last) ended on, still in LDS
@@ -1876,6 +1877,29 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_fused_epilogue(PrematSubgCon
   if (threadIdx.x == 0) out[r] = premat_subg_post(p, pre, qq);
 }
 
+// ============================================================ launchers ===
+static inline int last_err() { return (int)hipGetLastError(); }
+
+// The grid of a persistent kernel over `items` work items: one workgroup per resident slot (CUs x
+// workgroups per CU at `threads` and `lds` dynamic LDS bytes), at most one per item.  lds_limit
+// != 0 first raises the kernel's dynamic-LDS limit to it -- per call: the attribute is per device,
+// and one process may drive several GPUs (nothing here is cached across calls either).
+static int persistent_grid(const void* kernel, int threads, size_t lds, int64_t items, int64_t* grid,
+                           int lds_limit = 0) {
+  if (lds_limit != 0 &&
+      hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit) != hipSuccess)
+    return last_err();
+  int dev = 0, cus = 0, per_cu = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return last_err();
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return last_err();
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess)
+    return last_err();
+  const int64_t slots = (int64_t)cus * (per_cu < 1 ? 1 : per_cu);
+  *grid = items < slots ? items : slots;
+  return 0;
+}
+
 int launch_hrs_fused(const PrematSubgConst& c, uint64_t seed_ni, uint64_t seed_int,
                      int64_t rep_begin, int64_t reps, void* part, dcor_rep_out* out,
                      void* stream) {
@@ -1887,10 +1911,7 @@ int launch_hrs_fused(const PrematSubgConst& c, uint64_t seed_ni, uint64_t seed_i
   int bits = 1;
   while ((1ll << bits) < c.s.n) ++bits;
   hk.pa = bits / 2; hk.pc = bits - hk.pa;
-  const int wsel = [] {
-    const char* e = dcor::variant("DCOR_HRS_WPE");
-    return (e && std::atoi(e) == 4) ? 4 : 6;
-  }();
+  const int wsel = (int)dcor::variant("DCOR_HRS_WPE").as_int(6, 4, 4);
   const bool l2 = c.xyc != nullptr;  // uncoded panel: packed clips in HBM, indices in LDS
   const size_t lds = l2 ? (size_t)(20 * DICT_NW) * sizeof(double) +
                               (size_t)((c.s.k * c.s.m * 2 + 15) / 16) * 16
@@ -1905,17 +1926,8 @@ int launch_hrs_fused(const PrematSubgConst& c, uint64_t seed_ni, uint64_t seed_i
   const FusedK kern = wsel == 4 ? k_hrs_fused<4> : k_hrs_fused<6>;
   const FusedL2K kern_l2 = wsel == 4 ? k_hrs_fused_l2<4> : k_hrs_fused_l2<6>;
   const void* kf = l2 ? (const void*)kern_l2 : (const void*)kern;
-  // per call: the attribute is per device, and one process may drive several GPUs
-  if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-    return (int)hipGetLastError();
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return (int)hipGetLastError();
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kf, DICT_NT, lds) != hipSuccess)
-    return (int)hipGetLastError();
-  const int64_t slots = (int64_t)cus * (per_cu < 1 ? 1 : per_cu);
-  const int64_t grid = reps < slots ? reps : slots;
+  int64_t grid = 0;
+  if (int e = persistent_grid(kf, DICT_NT, lds, reps, &grid, kLdsDynMax)) return e;
   if (l2) {
     hipLaunchKernelGGL(kern_l2, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c,
                        hk, reps, (SubgPartial*)part);
@@ -1935,9 +1947,6 @@ int launch_hrs_fused(const PrematSubgConst& c, uint64_t seed_ni, uint64_t seed_i
                      (hipStream_t)stream, c, hk, (const SubgPartial*)part, out);
   return (int)hipGetLastError();
 }
-
-// ============================================================ launchers ===
-static inline int last_err() { return (int)hipGetLastError(); }
 
 int launch_premat_sign(const PrematSignConst& c, int64_t reps, dcor_rep_out* out, void* stream) {
   if (reps <= 0) return 0;
@@ -1964,12 +1973,7 @@ typedef void (*DictKernel)(PrematSubgConst, const uint16_t*, const double*, cons
 static DictKernel dict_kernel() {
   static const DictKernel ks[4] = {k_premat_subg_dict<4, 4, false>, k_premat_subg_dict<4, 6, false>,
                                    k_premat_subg_dict<8, 4, false>, k_premat_subg_dict<6, 6, false>};
-  const int v = [] {
-    const char* e = dcor::variant("DCOR_DICT_VARIANT");
-    const int x = e ? std::atoi(e) : 0;
-    return (x >= 0 && x < 4) ? x : 0;
-  }();
-  return ks[v];
+  return ks[dcor::variant("DCOR_DICT_VARIANT").as_int(0, 0, 3)];
 }
 
 // Uncoded shared-panel kernel variant (16-B loads in flight per thread, waves per SIMD);
@@ -1977,12 +1981,7 @@ static DictKernel dict_kernel() {
 static DictKernel l2_kernel() {
   static const DictKernel ks[4] = {k_premat_subg_dict<4, 8, true>, k_premat_subg_dict<4, 4, true>,
                                    k_premat_subg_dict<8, 8, true>, k_premat_subg_dict<8, 4, true>};
-  const int v = [] {
-    const char* e = dcor::variant("DCOR_L2_VARIANT");
-    const int x = e ? std::atoi(e) : 0;
-    return (x >= 0 && x < 4) ? x : 0;
-  }();
-  return ks[v];
+  return ks[dcor::variant("DCOR_L2_VARIANT").as_int(0, 0, 3)];
 }
 
 // Tiled uncoded-panel kernel variants (threads, batch pairs per thread per round, fill unroll,
@@ -2010,15 +2009,9 @@ struct TiledKernel {
 };
 // Where the tiled path's INT sums run (DCOR_TILED_INT): 0 inside the tiled kernel's first round of
 // tile fills; 1 (default) in k_premat_subg_int before it on the same stream; 2 in
-// k_premat_subg_int on the library's auxiliary stream beside it.
-static int tiled_int_mode() {
-  const int m = [] {
-    const char* e = dcor::variant("DCOR_TILED_INT");
-    const int x = e ? std::atoi(e) : 1;
-    return (x >= 0 && x <= 2) ? x : 1;
-  }();
-  return m;
-}
+// k_premat_subg_int on the library's auxiliary stream beside it.  The one parser of the switch:
+// premat_subg_run (dcor_capi.cpp) asks it whether to hand the auxiliary stream over.
+int tiled_int_mode() { return (int)dcor::variant("DCOR_TILED_INT").as_int(1, 0, 2); }
 #ifndef DCOR_INT_R
 #define DCOR_INT_R 4
 #endif
@@ -2028,46 +2021,16 @@ static TiledKernel tiled_kernel(bool intk, bool al) {
         {k_premat_subg_tiled<512, 5, 1, 1, 1, 4, true, true, true>, 512, 80 * 1024}},
        {{k_premat_subg_tiled<512, 5, 1, 1, 1, 4, true, false, false>, 512, 80 * 1024},
         {k_premat_subg_tiled<512, 5, 1, 1, 1, 4, true, false, true>, 512, 80 * 1024}}},
-      {{{k_premat_subg_tiled<1024, 5, 1, 1, 1, 4, true, true, false>, 1024, 160 * 1024},
-        {k_premat_subg_tiled<1024, 5, 1, 1, 1, 4, true, true, true>, 1024, 160 * 1024}},
-       {{k_premat_subg_tiled<1024, 5, 1, 1, 1, 4, true, false, false, 3>, 1024, 160 * 1024},
-        {k_premat_subg_tiled<1024, 5, 1, 1, 1, 4, true, false, true, 3>, 1024, 160 * 1024}}}};
-  const int v = [] {
-    const char* e = dcor::variant("DCOR_TILED_VARIANT");
-    const int x = e ? std::atoi(e) : 1;
-    return (x >= 0 && x < 2) ? x : 1;
-  }();
-  return ks[v][intk ? 0 : 1][al ? 1 : 0];
+      {{{k_premat_subg_tiled<1024, 5, 1, 1, 1, 4, true, true, false>, 1024, kLdsTiledMax},
+        {k_premat_subg_tiled<1024, 5, 1, 1, 1, 4, true, true, true>, 1024, kLdsTiledMax}},
+       {{k_premat_subg_tiled<1024, 5, 1, 1, 1, 4, true, false, false, 3>, 1024, kLdsTiledMax},
+        {k_premat_subg_tiled<1024, 5, 1, 1, 1, 4, true, false, true, 3>, 1024, kLdsTiledMax}}}};
+  return ks[dcor::variant("DCOR_TILED_VARIANT").as_int(1, 0, 1)][intk ? 0 : 1][al ? 1 : 0];
 }
-static bool tiled_enabled() {
-  const bool on = [] {
-    const char* e = dcor::variant("DCOR_TILED");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  return on;
-}
-
-// Workgroup slots of the coded-panel kernel (CUs x resident workgroups at this LDS size).
-static int premat_dict_slots(int64_t n, int* slots) {
-  const size_t lds = premat_dict_lds_bytes(n);
-  // per call: the attribute is per device, and one process may drive several GPUs
-  if (hipFuncSetAttribute((const void*)dict_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          150 * 1024) != hipSuccess)
-    return last_err();
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return last_err();
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return last_err();
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dict_kernel(), DICT_NT, lds) !=
-      hipSuccess)
-    return last_err();
-  *slots = cus * (per_cu < 1 ? 1 : per_cu);
-  return 0;
-}
+static bool tiled_enabled() { return !dcor::variant("DCOR_TILED").is("0"); }
 
 int launch_premat_subg(const PrematSubgConst& c0, int64_t reps, void* part, dcor_rep_out* out,
-                       void* stream, void* epi_stream, void* ev, void* int_stream, void* ev_fork,
-                       void* ev_join) {
+                       void* stream, const PrematAux& aux) {
   if (reps <= 0) return 0;
   PrematSubgConst c = c0;
   c.slices = 1;
@@ -2076,17 +2039,16 @@ int launch_premat_subg(const PrematSubgConst& c0, int64_t reps, void* part, dcor
     if (!c.dict_built)
       hipLaunchKernelGGL(k_panel_dict, dim3(1), dim3(DICT_THREADS), 0, (hipStream_t)stream, c.X,
                          c.Y, c.s.n, c.dict_codes, c.dict_vals, c.dict_ok);
-    int slots = 0;
-    if (int e = premat_dict_slots(c.s.n, &slots)) return e;
     // a prepared coded panel: no L2-gather kernel shares the partials, so replicates are
     // sliced.  The slice count is fixed (not sized to the launch), so a replicate's sums do
     // not depend on how replicates are split over launches or GPUs.
     if (c.dict_built == 2) c.slices = DCOR_DICT_SLICES;
-    const int64_t items = reps * c.slices;
-    const int64_t grid = items < (int64_t)slots ? items : (int64_t)slots;
-    hipLaunchKernelGGL(dict_kernel(), dim3((unsigned)grid), dim3(DICT_NT),
-                       premat_dict_lds_bytes(c.s.n), (hipStream_t)stream, c, c.dict_codes,
-                       c.dict_vals, c.dict_ok, reps, (SubgPartial*)part);
+    const DictKernel kd = dict_kernel();
+    const size_t lds = premat_dict_lds_bytes(c.s.n);
+    int64_t grid = 0;
+    if (int e = persistent_grid((const void*)kd, DICT_NT, lds, reps * c.slices, &grid, kLdsDynMax)) return e;
+    hipLaunchKernelGGL(kd, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c,
+                       c.dict_codes, c.dict_vals, c.dict_ok, reps, (SubgPartial*)part);
   }
   if (c.xyc != nullptr) {
     // shared panel, random batches, no dictionary (or the device probe may find none): the
@@ -2102,6 +2064,8 @@ int launch_premat_subg(const PrematSubgConst& c0, int64_t reps, void* part, dcor
     if (tiled) {
       // the INT sums in k_premat_subg_int: on the auxiliary stream when the caller gave one
       const int im = tiled_int_mode();
+      const hipStream_t int_stream = (hipStream_t)aux.int_stream;
+      const hipEvent_t ev_fork = (hipEvent_t)aux.ev_fork, ev_join = (hipEvent_t)aux.ev_join;
       const bool conc = im == 2 && int_stream != nullptr && ev_fork != nullptr && ev_join != nullptr;
       const bool intk = im == 0 || (im == 2 && !conc);
       // serial: before the tiled kernel; concurrent: submitted after it, so the tiled kernel's
@@ -2121,17 +2085,8 @@ int launch_premat_subg(const PrematSubgConst& c0, int64_t reps, void* part, dcor
       const int64_t ntiles = np > 0 ? (np + tp_max - 1) / tp_max : 1;
       const int64_t tile_pairs = np > 0 ? (np + ntiles - 1) / ntiles : 1;
       const size_t lds = red_b + (size_t)(2 * tile_pairs + 3) * 16;
-      if (hipFuncSetAttribute((const void*)tk.k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024) != hipSuccess)
-        return last_err();
-      int dev = 0, cus = 0, per_cu = 0;
-      if (hipGetDevice(&dev) != hipSuccess) return last_err();
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return last_err();
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tk.k, tk.nt, lds) != hipSuccess)
-        return last_err();
-      const int64_t slots = (int64_t)cus * (per_cu < 1 ? 1 : per_cu);
-      const int64_t grid = reps < slots ? reps : slots;
+      int64_t grid = 0;
+      if (int e = persistent_grid((const void*)tk.k, tk.nt, lds, reps, &grid, kLdsTiledMax)) return e;
       hipLaunchKernelGGL(tk.k, dim3((unsigned)grid), dim3((unsigned)tk.nt), lds, (hipStream_t)stream, c,
                          (const int*)c.dict_ok, reps, tile_pairs, (SubgPartial*)part);
       if (conc) {
@@ -2143,14 +2098,8 @@ int launch_premat_subg(const PrematSubgConst& c0, int64_t reps, void* part, dcor
     } else if (c.dict_built != 2) {
       const DictKernel kl = l2_kernel();
       const size_t lds = (size_t)(20 * DICT_NW) * sizeof(double);
-      int dev = 0, cus = 0, per_cu = 0;
-      if (hipGetDevice(&dev) != hipSuccess) return last_err();
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return last_err();
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kl, DICT_NT, lds) != hipSuccess)
-        return last_err();
-      const int64_t slots = (int64_t)cus * (per_cu < 1 ? 1 : per_cu);
-      const int64_t grid = reps < slots ? reps : slots;
+      int64_t grid = 0;
+      if (int e = persistent_grid((const void*)kl, DICT_NT, lds, reps, &grid)) return e;
       hipLaunchKernelGGL(kl, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c,
                          (const uint16_t*)nullptr, (const double*)nullptr, (const int*)c.dict_ok,
                          reps, (SubgPartial*)part);
@@ -2161,15 +2110,12 @@ int launch_premat_subg(const PrematSubgConst& c0, int64_t reps, void* part, dcor
   }
   // workgroup-per-replicate epilogue: measured faster here than the wave-per-replicate form
   // (k_premat_subg_epilogue_w: 2000 loaded keys per wave cost 200+ VGPRs, one wave per SIMD)
-  const int wave_epi = [] {
-    const char* v = dcor::variant("DCOR_EPILOGUE");
-    return v && std::strcmp(v, "wave") == 0;
-  }();
+  const bool wave_epi = dcor::variant("DCOR_EPILOGUE").is("wave");
   const unsigned gw = (unsigned)((reps + DCOR_WAVES - 1) / DCOR_WAVES);
-  if (epi_stream != nullptr) {  // epilogue on a second stream, after this chunk's streaming
-    if (hipEventRecord((hipEvent_t)ev, (hipStream_t)stream) != hipSuccess) return last_err();
-    if (hipStreamWaitEvent((hipStream_t)epi_stream, (hipEvent_t)ev, 0) != hipSuccess) return last_err();
-    stream = epi_stream;
+  if (aux.epi_stream != nullptr) {  // epilogue on a second stream, after this chunk's streaming
+    if (hipEventRecord((hipEvent_t)aux.epi_event, (hipStream_t)stream) != hipSuccess) return last_err();
+    if (hipStreamWaitEvent((hipStream_t)aux.epi_stream, (hipEvent_t)aux.epi_event, 0) != hipSuccess) return last_err();
+    stream = aux.epi_stream;
   }
   if (!wave_epi)
     hipLaunchKernelGGL(k_premat_subg_epilogue, dim3((unsigned)reps), dim3(DCOR_BLOCK), 0,

@@ -1091,7 +1091,7 @@ int launch_rs_hrs_ni(const int32_t* d_seeds, int64_t runs, int64_t n, int64_t km
   const size_t lds = rs_hrs_ni_lds_bytes(n);
   // per call: the attribute is per device, and one process may drive several GPUs
   const hipError_t e = hipFuncSetAttribute((const void*)k_rs_hrs_ni,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsDynMax);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(k_rs_hrs_ni, dim3((unsigned)runs), dim3(64), lds, (hipStream_t)stream, d_seeds,
                      n, km, k, perm, lx, ly);
@@ -1107,7 +1107,7 @@ int launch_rs_materialise(const RsCell* d_cells, int ncells, int32_t rc, void* s
   if (lds > 64 * 1024) {
     // per call: the attribute is per device, and one process may drive several GPUs
     const hipError_t e = hipFuncSetAttribute((const void*)k_rs_materialise,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsDynMax);
     if (e != hipSuccess) return (int)e;
   }
   hipLaunchKernelGGL(k_rs_materialise, dim3((unsigned)(ncells * rc)), dim3(256), lds,

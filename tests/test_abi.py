@@ -125,6 +125,18 @@ def test_hrs_sweep_argument_checks_without_gpu():
     assert _lib.lib.dcor_hrs_sweep_launch(C.byref(base), None, seg, 1, C.c_void_p(8), None) == _lib.DCOR_EINVAL
 
 
+def test_replicate_range_checked_without_overflow():
+    """[rep_begin, rep_begin + reps) must stay below 2^32 - 1; the check neither forms the sum (a
+    huge rep_begin is rejected, not wrapped) nor needs a device (nothing would be launched: count 0)."""
+    from dcor import _lib
+    draws = lambda rb: _lib.lib.dcor_draws_launch(0, 1, 11, rb, 2, 0, None, None)
+    perm = lambda rb: _lib.lib.dcor_perm_launch(1, 1, rb, 2, 10, 0, None, None)
+    for call in (draws, perm):
+        assert call(0xfffffffe) == _lib.DCOR_EINVAL
+        assert call(2**63 - 2) == _lib.DCOR_EINVAL
+        assert call(0xfffffffd) != _lib.DCOR_EINVAL   # DCOR_ENODEV without a GPU, DCOR_OK with one
+
+
 def test_accum_merge_and_finalize_host():
     """dcor_accum_merge / finalize are host helpers: mse, bias, var, coverage, ci_length."""
     from dcor import _lib

@@ -205,6 +205,11 @@ def test_sweep_launch_checks_every_segment_first(panel):
             assert st == _lib.DCOR_EINVAL, field
         far = (_lib.HrsSegment * 1)(_lib.HrsSegment(eps=2.0, seed_ni=1, seed_int=2, rep_begin=2**32 - 2, reps=4))
         assert _lib.lib.dcor_hrs_sweep_launch(C.byref(base), pn, far, 1, C.c_void_p(out.data_ptr()), sp) == _lib.DCOR_EINVAL
+        # a range whose end overflows int64 is rejected like any other, with nothing allocated
+        huge = (_lib.HrsSegment * 1)(_lib.HrsSegment(eps=2.0, seed_ni=1, seed_int=2, rep_begin=2**63 - 2, reps=2))
+        allocs = _lib.lib.dcor_alloc_count()
+        assert _lib.lib.dcor_hrs_sweep_launch(C.byref(base), pn, huge, 1, C.c_void_p(out.data_ptr()), sp) == _lib.DCOR_EINVAL
+        assert _lib.lib.dcor_alloc_count() == allocs
         torch.cuda.synchronize()
         assert bool((out == 7.0).all())
         empty = (_lib.HrsSegment * 1)(_lib.HrsSegment(eps=2.0, reps=0, out_row=0))
