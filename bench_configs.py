@@ -413,6 +413,26 @@ def hrs_sweep(R):
               "from one native call (hrs.sweep_segments), summaries (means, type-7 quantiles) on the host")
 
 
+def hrs_sweep_fused(R):
+    """HS with the noise drawn inside the kernels (dcor_hrs_fused_sweep_launch): the same panel, eps
+    grid, keys and R, every eps in one streaming launch and one epilogue launch, no HBM noise."""
+    import numpy as np
+    import torch
+    from dcor import hrs
+    args = hrs_panel("coded")
+    hrs.eps_sweep(*args, reps=R, mode="fused")    # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = hrs.eps_sweep(*args, reps=R, mode="fused")
+    torch.cuda.synchronize()
+    t = time.perf_counter() - t0
+    total = len(hrs.EPS_GRID) * R
+    line("HSf", replicates=total, seconds=t, reps_per_s=total / t, finite=bool(np.isfinite(res["runs"]).all()),
+         mode="fused", kernel="k_hrs_sweep_fused (LDS codes, per-segment constants from a device table)",
+         note="23 eps x R NI + INT runs on the coded stand-in panel, encoded once, every eps in one launch of the "
+              "in-kernel-noise kernels (hrs.sweep_segments(mode='fused')), summaries on the host")
+
+
 def subg():
     from dcor.sim import CellSpec, simulate
     cell = CellSpec(n=100_000, rho=0.5, eps1=1.0, eps2=1.0, family="subG", dgp="bounded_factor", seed=5)
@@ -569,7 +589,7 @@ def dist_hrs(name, world, rank, dry_run, R, mode, panel="coded", sweep=False):
     args = hrs_panel(panel)
     if sweep:
         def run():
-            return eps_sweep_distributed(*args, reps=R)["runs"].reshape(-1, 6)
+            return eps_sweep_distributed(*args, reps=R, mode=mode)["runs"].reshape(-1, 6)
     else:
         def run():
             return run_hrs_distributed(*args, 2.0, R, mode=mode, chunk=65536 if mode == "fused" else 8192)
@@ -618,7 +638,7 @@ def dist_c5(world, rank, dry_run, R):
 
 def main_dist(a, world, rank, local):
     """bench_configs.py under N ranks: C3, C4 and the HRS workload (C5 weak; C5-e2e, C5-fused,
-    C5-fused-continuous and the eps sweep HS strong) -- every config that shards."""
+    C5-fused-continuous and the eps sweeps HS / HSf strong) -- every config that shards."""
     import torch.distributed as dist
     which = a.only.split(",")
     if a.dry_run:
@@ -652,12 +672,14 @@ def main_dist(a, world, rank, local):
         dist_hrs("C5-fused-continuous", world, rank, a.dry_run, a.c5e_R, "fused", panel="continuous")
     if "HS" in which:
         dist_hrs("HS", world, rank, a.dry_run, a.hs_R, "premat", sweep=True)
+    if "HSf" in which:
+        dist_hrs("HSf", world, rank, a.dry_run, a.hs_R, "fused", sweep=True)
     if "C4" in which:
         ok, small, big, nskip = c4_cells()
         dist_grid("C4", [(small, a.c4_B), (big, a.c4_B_big)], world, rank, a.dry_run, cells=len(ok),
                   cells_skipped_k_lt_1=nskip, reps_per_cell=a.c4_B, reps_per_cell_n1e6=a.c4_B_big,
                   cells_n1e6=len(big))
-    others = [w for w in which if w not in ("C3", "C4", "C5", "C5e", "C5f", "C5fc", "HS")]
+    others = [w for w in which if w not in ("C3", "C4", "C5", "C5e", "C5f", "C5fc", "HS", "HSf")]
     if others and rank == 0:
         print(json.dumps({"skipped": others, "reason": "single-GPU configs: run without --gpus"}), flush=True)
     dist.destroy_process_group()
@@ -665,7 +687,7 @@ def main_dist(a, world, rank, local):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="C1,C2,C3,C4,VG,SG,C5,C5c,C5e,C5f,C5fc,HS,S,R1,RG,RH")
+    ap.add_argument("--only", default="C1,C2,C3,C4,VG,SG,C5,C5c,C5e,C5f,C5fc,HS,HSf,S,R1,RG,RH")
     ap.add_argument("--c3-reps", type=int, default=100_000)
     ap.add_argument("--c3-eps", default=None, help="subset of C3's eps pairs, e.g. 0.5x0.5,1.5x0.5")
     ap.add_argument("--c4-B", type=int, default=1000)
@@ -674,7 +696,7 @@ def main():
     ap.add_argument("--c5e-R", type=int, default=1_000_000)
     ap.add_argument("--hs-R", type=int, default=200, help="runs per eps of the HRS sweep (real-data-sims.R: R = 200)")
     ap.add_argument("--gpus", type=int, default=None,
-                    help="C3, C4, C5, C5e, C5f, C5fc, HS over N ranks (one per GPU); without a launcher's WORLD_SIZE, N rank processes "
+                    help="C3, C4, C5, C5e, C5f, C5fc, HS, HSf over N ranks (one per GPU); without a launcher's WORLD_SIZE, N rank processes "
                          "are started")
     ap.add_argument("--variant", action="append", default=[], metavar="NAME=VALUE",
                     help="engine implementation switch for A/B runs (dcor_set_variant; repeatable)")
@@ -713,6 +735,7 @@ def main():
     if "C5f" in which: c5_fused(a.c5e_R)
     if "C5fc" in which: c5_fused(a.c5e_R, panel="continuous")
     if "HS" in which: hrs_sweep(a.hs_R)
+    if "HSf" in which: hrs_sweep_fused(a.hs_R)
     if "S" in which: subg()
     if "R1" in which: rstream_c1()
     if "RG" in which: rstream_grid()

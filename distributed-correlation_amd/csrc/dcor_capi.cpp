@@ -1336,6 +1336,125 @@ int dcor_hrs_sweep_launch(const dcor_premat_subg* base, const dcor_panel* panel,
   return e;
 }
 
+// Fused sweep scratch: partials (one SubgPartial per replicate of the call) | the segment table |
+// pack (xyc | soc, uncoded panel).  Every region starts 256-B aligned when the base is.
+struct FusedSweepLayout {
+  int64_t n;
+  size_t tab_off, pack_off, bytes;
+  FusedSweepLayout(int64_t items, int64_t nseg, int64_t n_, bool pack)
+      : n(n_), tab_off(al256((size_t)items * sizeof(SubgPartial))),
+        pack_off(tab_off + al256((size_t)nseg * sizeof(HrsSegConst))),
+        bytes(pack_off + (pack ? (size_t)n_ * 2 * sizeof(double2) : 0)) {}
+  HrsSegConst* tab(void* base) const { return (HrsSegConst*)((char*)base + tab_off); }
+  double2* xyc(void* base) const { return (double2*)((char*)base + pack_off); }
+  double2* soc(void* base) const { return xyc(base) + n; }
+};
+
+int dcor_hrs_fused_sweep_launch(const dcor_premat_subg* base, const dcor_panel* panel,
+                                const dcor_hrs_segment* segs, int64_t nseg, dcor_rep_out* d_out,
+                                void* stream) {
+  if (!base || !panel || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
+    return fail(DCOR_EINVAL, "hrs_fused_sweep: null argument");
+  if (nseg == 0) return DCOR_OK;   // nothing to check against the panel, nothing to run
+  // the segments' own fields first (they need nothing but segs), then the panel and base, then
+  // every segment's launch constants: nothing is enqueued for an invalid sweep
+  int64_t items = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_hrs_segment& g = segs[i];
+    if (g.reps < 0 || g.rep_begin < 0 || g.out_row < 0 || !(g.eps > 0.0))
+      return fail(DCOR_EINVAL, "hrs_fused_sweep: segment %lld: need eps > 0, reps, rep_begin, out_row >= 0",
+                  (long long)i);
+    if (rep_range_exceeds(g.rep_begin, g.reps))
+      return fail(DCOR_EINVAL, "hrs_fused_sweep: segment %lld: replicate range exceeds 2^32", (long long)i);
+    items += g.reps;   // reps <= 2^32 each: no overflow below 2^31 segments
+    if (items > 0x7fffffffLL)
+      return fail(DCOR_EINVAL, "hrs_fused_sweep: more than 2^31 - 1 replicates in one call");
+  }
+  if (base->X != panel->X || base->Y != panel->Y || base->xy_stride != 0 || base->n != panel->n)
+    return fail(DCOR_EINVAL, "hrs_fused_sweep: X, Y, n must be the panel's and xy_stride 0");
+  if (!base->hrs) return fail(DCOR_EINVAL, "hrs_fused_sweep: the HRS variant only (hrs = 1)");
+  if (!(base->delta > 0.0)) return fail(DCOR_EINVAL, "hrs_fused_sweep: delta must be positive");
+  std::vector<dcor_premat_subg> qs((size_t)nseg);
+  std::vector<HrsSegConst> tab;
+  PrematSubgConst p0;      // the first segment's constants: the sweep-wide ones are read from it
+  bool wide = true;        // the sweep-wide constants are the same in every segment
+  int64_t max_km = 0, first = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_hrs_segment& g = segs[i];
+    dcor_premat_subg& q = qs[(size_t)i];
+    q = *base;
+    q.reps = g.reps;
+    q.eps1 = q.eps2 = g.eps;
+    q.eta1 = q.eta2 = 1.0;
+    q.lam_r = dcor_lambda_receiver_from_noise(base->lam_s, base->lam_o, g.eps, base->delta);
+    PrematSubgConst pc;
+    if (int st = premat_subg_const(&q, pc)) return st;
+    if (g.reps == 0) continue;
+    if (tab.empty()) p0 = pc;
+    const SubgConst &a = pc.s, &b = p0.s;
+    // bitwise: a NaN clip (lam_s / lam_o unset with an out-of-range eta) differs from itself in
+    // value but not as a constant
+    const double wa[] = {a.l1, a.l2, a.ls, pc.lo_, a.nd, a.sqrt_n, a.crit};
+    const double wb[] = {b.l1, b.l2, b.ls, p0.lo_, b.nd, b.sqrt_n, b.crit};
+    wide = wide && std::memcmp(wa, wb, sizeof(wa)) == 0 && a.sender_is_X == b.sender_is_X &&
+           std::memcmp(&a.mix, &b.mix, sizeof(a.mix)) == 0;
+    HrsSegConst t;
+    std::memset(&t, 0, sizeof(t));
+    t.k = a.k; t.m = a.m; t.md_pow2 = a.md_pow2;
+    t.md = a.md; t.kd = a.kd; t.inv_md = a.inv_md;
+    t.bx = a.bx; t.by = a.by; t.m_over_k = a.m_over_k; t.sqrt_k = a.sqrt_k;
+    t.lr = a.lr; t.bs = a.bs; t.s_central = a.s_central; t.sn2x2 = a.sn2x2; t.eps_r = a.eps_r;
+    t.crit_sqrt2_s = pc.crit_sqrt2_s;
+    t.ni0 = (uint32_t)g.seed_ni; t.ni1 = (uint32_t)(g.seed_ni >> 32);
+    t.in0 = (uint32_t)g.seed_int; t.in1 = (uint32_t)(g.seed_int >> 32);
+    t.rep_begin = (uint32_t)g.rep_begin;
+    t.first = first; t.out_row = g.out_row;
+    first += g.reps;
+    tab.push_back(t);
+    max_km = std::max(max_km, a.k * (int64_t)a.m);
+  }
+  if (items == 0) return DCOR_OK;
+  if (int st = need_device()) return st;
+  // DCOR_HRS_FUSED_L2=1 runs a coded panel through the uncoded kernel, as in dcor_hrs_fused_launch
+  const bool coded = panel->coded && !dcor::variant("DCOR_HRS_FUSED_L2").is("1");
+  if ((!coded && base->n > DCOR_DICT_NMAX) || !wide) {
+    // an uncoded panel too large for the LDS index row has no fused kernel (hrs_fused_materialised),
+    // and clips that differ between segments (lam_s / lam_o unset) have no sweep-wide dictionary:
+    // the segments one by one, each the per-segment entry itself
+    for (int64_t i = 0; i < nseg; ++i) {
+      if (segs[i].reps == 0) continue;
+      if (int e = dcor_hrs_fused_launch(&qs[(size_t)i], panel, segs[i].seed_ni, segs[i].seed_int,
+                                        segs[i].rep_begin, d_out + segs[i].out_row, stream))
+        return e;
+    }
+    return DCOR_OK;
+  }
+  PrematSubgConst p = p0;
+  p.perm = nullptr; p.lap_ni_x = p.lap_ni_y = p.lap_local = p.lap_central = nullptr;
+  p.mix_z = p.mix_l = nullptr;
+  if (coded) {
+    p.dict_codes = panel->codes(); p.dict_vals = panel->dict(); p.dict_ok = panel->ok();
+    p.dict_built = 2;
+  }
+  const FusedSweepLayout lay(items, (int64_t)tab.size(), base->n, !coded);
+  void* buf = nullptr;
+  const hipStream_t st = (hipStream_t)stream;
+  if (hipMallocAsync(&buf, lay.bytes, st) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(DCOR_ENOMEM, "hrs_fused_sweep: cannot allocate %zu scratch bytes", lay.bytes);
+  }
+  count_alloc();
+  if (!coded) { p.xyc = lay.xyc(buf); p.soc = lay.soc(buf); }
+  // from pageable memory: the copy has left `tab` when the call returns
+  int rc = (int)hipMemcpyAsync(lay.tab(buf), tab.data(), tab.size() * sizeof(HrsSegConst),
+                               hipMemcpyHostToDevice, st);
+  if (!rc)
+    rc = launch_hrs_fused_sweep(p, lay.tab(buf), (int)tab.size(), items, max_km, buf, d_out, stream);
+  (void)hipFreeAsync(buf, st);
+  if (rc) return hip_fail((hipError_t)rc, "hrs_fused_sweep launch");
+  return DCOR_OK;
+}
+
 int dcor_panel_dict_probe(const double* d_X, const double* d_Y, int64_t n, int* ok) {
   if (!d_X || !d_Y || !ok || n < 1) return fail(DCOR_EINVAL, "panel_dict_probe: bad arguments");
   if (int st = need_device()) return st;

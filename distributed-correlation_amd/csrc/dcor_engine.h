@@ -319,6 +319,30 @@ int launch_premat_sign(const PrematSignConst& c, int64_t reps, dcor_rep_out* out
 // scratch the launch packs; n <= DCOR_DICT_NMAX); part: reps * 80 B.
 int launch_hrs_fused(const PrematSubgConst& c, uint64_t seed_ni, uint64_t seed_int,
                      int64_t rep_begin, int64_t reps, void* part, dcor_rep_out* out, void* stream);
+// One segment of a fused HRS sweep (dcor_hrs_fused_sweep_launch): the constants of
+// PrematSubgConst that depend on the segment's eps (make_subg's values, unchanged), its Philox
+// keys and its place in the call.  The launch's device table holds the segments with reps > 0 in
+// call order, so `first` is strictly increasing; everything else (n, the clips l1 / l2 / ls / lo_,
+// sender_is_X, nd, sqrt_n, crit, mix) is the same for every segment and stays a kernel argument.
+struct HrsSegConst {
+  int64_t k;
+  int32_t m, md_pow2;
+  double md, kd, inv_md;
+  double bx, by, m_over_k, sqrt_k;
+  double lr, bs, s_central, sn2x2, eps_r, crit_sqrt2_s;
+  uint32_t ni0, ni1, in0, in1;   // Philox keys (seed_ni, seed_int)
+  uint32_t rep_begin, pad;
+  int64_t first;                 // the segment's first work item: the sum of the reps before it
+  int64_t out_row;
+};
+static_assert(sizeof(HrsSegConst) == 160, "the sweep's device table stride");
+// The segments `tab` (device, nseg >= 1 entries, `items` replicates in all) of a fused HRS sweep
+// in one streaming launch and one epilogue launch.  c: the sweep-wide constants and the panel as
+// for launch_hrs_fused (any segment's PrematSubgConst); max_km: the largest k m of the segments;
+// part: items * 80 B.  Item i of segment s is replicate s.rep_begin + (i - s.first), record
+// out[s.out_row + (i - s.first)].
+int launch_hrs_fused_sweep(const PrematSubgConst& c, const HrsSegConst* tab, int nseg, int64_t items,
+                           int64_t max_km, void* part, dcor_rep_out* out, void* stream);
 // The auxiliary streams and events a premat sub-G launch may use; default: none.
 struct PrematAux {
   // if non-null the epilogue runs on epi_stream after epi_event, recorded on `stream` behind the

@@ -1539,6 +1539,173 @@ struct HrsKeys {
 #define HRS_SITE_MIX_Z 15u
 #define HRS_SITE_MIX_L 16u
 
+// One replicate of the coded fused kernels (k_hrs_fused, k_hrs_sweep_fused): the workgroup's sums
+// of replicate `rep` under constants p and keys hk into *dst.  dX / dY / dS / dO: the clipped
+// dictionaries and cod: the panel codes, in LDS; gs: this workgroup's scratch row (k m u16,
+// L2-resident); red: the two reduction buffers (10 DICT_NW doubles each) and par: the one this
+// item takes, alternating from item to item of a workgroup.  Every
+// thread of the workgroup calls it; it holds two barriers.
+__device__ __forceinline__ void hrs_fused_item(const PrematSubgConst& p, const HrsKeys& hk,
+                                               uint32_t rep, const double* dX, const double* dY,
+                                               const double* dS, const double* dO,
+                                               const uint16_t* cod, uint16_t* __restrict__ gs,
+                                               double* red, int par, SubgPartial* __restrict__ dst) {
+  const SubgConst& c = p.s;
+  const int tid = threadIdx.x;
+  const uint32_t n = (uint32_t)c.n;
+  DD sP{0, 0}, sT{0, 0}, sT2{0, 0}, sU{0, 0}, sU2{0, 0};
+  auto uval = [&](uint32_t cd, double l) {  // real-data-sims.R:222-232
+    // finite dictionary (k_panel_dict) and noise: the product is never NaN
+    return rclip_fin((dS[cd & 255u] + c.bs * l) * dO[cd >> 8], c.lr);
+  };
+  auto uterm = [&](double Uc) {
+    ks_acc(sU, Uc);
+    ks_acc(sU2, Uc * Uc);
+  };
+  // a pair of INT terms (of NI batches) is added plainly and the pair sum compensated: half
+  // the TwoSum chains of per-term sums
+  auto uterm2 = [&](double U0, double U1) {
+    ks_acc(sU, U0 + U1);
+    ks_acc(sU2, U0 * U0 + U1 * U1);
+  };
+  // Phase A: the panel codes at the permuted batch slots, gs[t] = code[P(t)], t < k m, into
+  // this workgroup's scratch row (L2-resident, reused by every replicate of the workgroup).
+  // Each lane walks its strided run of t and moves to the next t as soon as a walk lands,
+  // so lanes stay busy while walk lengths differ.  Phase B reads the row after a barrier.
+  const U4 kk = draw(0u, rep, DCOR_SITE_PERM, hk.ni0, hk.ni1);
+  {
+    const uint32_t km = (uint32_t)(c.k * c.m);
+    uint32_t t = (uint32_t)tid, x = t;
+    while (t < km) {
+      x = feistel_pass(x, hk.pa, hk.pc, kk);
+      if (x < n) {
+        gs[t] = cod[x];
+        t += DICT_NT;
+        x = t;
+      }
+    }
+  }
+  {  // INT local noise: block b -> samples 2b, 2b+1
+    const int64_t nb = c.n >> 1;
+    for (int64_t b = tid; b < nb; b += DICT_NT) {
+      const U4 w = draw((uint32_t)b, rep, HRS_SITE_LOCAL, hk.in0, hk.in1);
+      uterm2(uval(cod[2 * b], unit_laplace(u53(w.w0, w.w1))),
+             uval(cod[2 * b + 1], unit_laplace(u53(w.w2, w.w3))));
+    }
+    if ((c.n & 1) && tid == DICT_NT - 1) {
+      const U4 w = draw((uint32_t)nb, rep, HRS_SITE_LOCAL, hk.in0, hk.in1);
+      uterm(uval(cod[c.n - 1], unit_laplace(u53(w.w0, w.w1))));
+    }
+  }
+  double* rb = red + (par & 1) * (10 * DICT_NW);
+  auto wave_put = [&](int v, DD a) {
+    a = wave_sum_dd(a);
+    if ((tid & 63) == 0) {
+      rb[(2 * v) * DICT_NW + (tid >> 6)] = a.hi;
+      rb[(2 * v + 1) * DICT_NW + (tid >> 6)] = a.lo;
+    }
+  };
+  wave_put(3, sU);
+  wave_put(4, sU2);
+  __syncthreads();  // phase A's scratch row is complete
+  auto nterm = [&](double xt, double yt) {  // real-data-sims.R:133-137
+    ks_acc(sP, xt * yt);
+    const double T = c.md * xt * yt;
+    ks_acc(sT, T);
+    ks_acc(sT2, T * T);
+  };
+  auto nterm2 = [&](double xt0, double yt0, double xt1, double yt1) {
+    const double T0 = c.md * xt0 * yt0, T1 = c.md * xt1 * yt1;
+    ks_acc(sP, xt0 * yt0 + xt1 * yt1);
+    ks_acc(sT, T0 + T1);
+    ks_acc(sT2, T0 * T0 + T1 * T1);
+  };
+  if (c.m == 2) {  // batches 2q, 2q+1 share one Philox block of X noise and one of Y noise
+    const uint32_t* __restrict__ g2 = reinterpret_cast<const uint32_t*>(gs);  // batch j's codes
+    auto xt_of = [&](uint32_t ab, double lxj) {
+      return (dX[(ab & 0xFFFFu) & 255u] + dX[(ab >> 16) & 255u]) * 0.5 + c.bx * lxj;
+    };
+    auto yt_of = [&](uint32_t ab, double lyj) {
+      return (dY[(ab & 0xFFFFu) >> 8] + dY[(ab >> 16) >> 8]) * 0.5 + c.by * lyj;
+    };
+    for (int64_t q = tid; 2 * q < c.k; q += DICT_NT) {
+      const U4 wx = draw((uint32_t)q, rep, HRS_SITE_NI_X, hk.ni0, hk.ni1);
+      const U4 wy = draw((uint32_t)q, rep, HRS_SITE_NI_Y, hk.ni0, hk.ni1);
+      const uint32_t ab0 = g2[2 * q];
+      const double xt0 = xt_of(ab0, unit_laplace(u53(wx.w0, wx.w1)));
+      const double yt0 = yt_of(ab0, unit_laplace(u53(wy.w0, wy.w1)));
+      if (2 * q + 1 < c.k) {
+        const uint32_t ab1 = g2[2 * q + 1];
+        nterm2(xt0, yt0, xt_of(ab1, unit_laplace(u53(wx.w2, wx.w3))),
+               yt_of(ab1, unit_laplace(u53(wy.w2, wy.w3))));
+      } else {
+        nterm(xt0, yt0);
+      }
+    }
+  } else {
+    for (int64_t j = tid; j < c.k; j += DICT_NT) {
+      const U4 wx = draw((uint32_t)(j >> 1), rep, HRS_SITE_NI_X, hk.ni0, hk.ni1);
+      const U4 wy = draw((uint32_t)(j >> 1), rep, HRS_SITE_NI_Y, hk.ni0, hk.ni1);
+      const double lxj = unit_laplace((j & 1) ? u53(wx.w2, wx.w3) : u53(wx.w0, wx.w1));
+      const double lyj = unit_laplace((j & 1) ? u53(wy.w2, wy.w3) : u53(wy.w0, wy.w1));
+      DD bx{0, 0}, by{0, 0};
+      for (int r = 0; r < c.m; ++r) {
+        const uint32_t a = gs[j * c.m + r];
+        dd_acc(bx, dX[a & 255u]);
+        dd_acc(by, dY[a >> 8]);
+      }
+      const DD xb = dd_div_d(bx, c.md), yb = dd_div_d(by, c.md);
+      nterm((xb.hi + xb.lo) + c.bx * lxj, (yb.hi + yb.lo) + c.by * lyj);
+    }
+  }
+  wave_put(0, sP);
+  wave_put(1, sT);
+  wave_put(2, sT2);
+  __syncthreads();
+  if (tid < 5) {
+    const DD a = fold_waves_dd<DICT_NW>(rb + (2 * tid) * DICT_NW, rb + (2 * tid + 1) * DICT_NW);
+    dst->s[2 * tid] = a.hi;
+    dst->s[2 * tid + 1] = a.lo;
+  }
+}
+
+// The coded fused kernels' dynamic LDS (premat_dict_lds_bytes(n)), filled once per workgroup: the
+// four clipped dictionaries (the clips are the same for every replicate and every eps), the two
+// reduction buffers, the panel codes.  Ends with a barrier.
+struct HrsLds {
+  double *dX, *dY, *dS, *dO, *red;
+  uint16_t* cod;
+};
+__device__ __forceinline__ HrsLds hrs_fused_setup(const PrematSubgConst& p,
+                                                  const uint16_t* __restrict__ codes_g,
+                                                  const double* __restrict__ dict_g, double* dsm) {
+  const SubgConst& c = p.s;
+  const int tid = threadIdx.x;
+  HrsLds L;
+  L.dX = dsm;
+  L.dY = dsm + DICT_MAX;
+  L.dS = dsm + 2 * DICT_MAX;
+  L.dO = dsm + 3 * DICT_MAX;
+  L.red = dsm + 4 * DICT_MAX;
+  L.cod = reinterpret_cast<uint16_t*>(dsm + 4 * DICT_MAX + 20 * DICT_NW);
+  if (tid < DICT_MAX) {
+    const double x = dict_g[tid], y = dict_g[DICT_MAX + tid];
+    L.dX[tid] = rclip(x, c.l1);
+    L.dY[tid] = rclip(y, c.l2);
+    const double sv = c.sender_is_X ? x : y, ov = c.sender_is_X ? y : x;
+    L.dS[tid] = rclip(sv, c.ls);
+    L.dO[tid] = rclip(ov, p.lo_);
+  }
+  {
+    const int64_t nv = (c.n * 2 + 15) / 16;
+    const uint4* src = reinterpret_cast<const uint4*>(codes_g);
+    uint4* dst = reinterpret_cast<uint4*>(L.cod);
+    for (int64_t w = tid; w < nv; w += DICT_NT) dst[w] = src[w];
+  }
+  __syncthreads();
+  return L;
+}
+
 template <int WPE>
 __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_fused(PrematSubgConst p, HrsKeys hk,
                                                            const uint16_t* __restrict__ codes_g,
@@ -1548,147 +1715,129 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_fused(PrematSubgConst p, H
                                                            uint16_t* __restrict__ scr,
                                                            int64_t scr_stride) {
   extern __shared__ double dsm[];
+  const HrsLds L = hrs_fused_setup(p, codes_g, dict_g, dsm);
+  for (int64_t it = blockIdx.x; it < reps; it += gridDim.x) {
+    hrs_fused_item(p, hk, hk.rep_begin + (uint32_t)it, L.dX, L.dY, L.dS, L.dO, L.cod,
+                   scr + (int64_t)blockIdx.x * scr_stride,
+                   L.red, (int)((it - blockIdx.x) / gridDim.x), part + it);
+  }
+}
+
+// One replicate of the uncoded fused kernels (k_hrs_fused_l2, k_hrs_sweep_fused_l2), as
+// hrs_fused_item: gs is the workgroup's LDS index row (k m u16), the clipped panel p.xyc / p.soc
+// is gathered from L2.
+__device__ __forceinline__ void hrs_fused_l2_item(const PrematSubgConst& p, const HrsKeys& hk,
+                                                  uint32_t rep, uint16_t* gs, double* red, int par,
+                                                  SubgPartial* __restrict__ dst) {
   const SubgConst& c = p.s;
   const int tid = threadIdx.x;
-  double* dX = dsm;
-  double* dY = dsm + DICT_MAX;
-  double* dS = dsm + 2 * DICT_MAX;
-  double* dO = dsm + 3 * DICT_MAX;
-  double* red = dsm + 4 * DICT_MAX;
-  uint16_t* cod = reinterpret_cast<uint16_t*>(dsm + 4 * DICT_MAX + 20 * DICT_NW);
-  if (tid < DICT_MAX) {
-    const double x = dict_g[tid], y = dict_g[DICT_MAX + tid];
-    dX[tid] = rclip(x, c.l1);
-    dY[tid] = rclip(y, c.l2);
-    const double sv = c.sender_is_X ? x : y, ov = c.sender_is_X ? y : x;
-    dS[tid] = rclip(sv, c.ls);
-    dO[tid] = rclip(ov, p.lo_);
-  }
-  {
-    const int64_t nv = (c.n * 2 + 15) / 16;
-    const uint4* src = reinterpret_cast<const uint4*>(codes_g);
-    uint4* dst = reinterpret_cast<uint4*>(cod);
-    for (int64_t w = tid; w < nv; w += DICT_NT) dst[w] = src[w];
-  }
-  __syncthreads();
+  const double2* __restrict__ xy = p.xyc;
+  const double2* __restrict__ so = p.soc;
   const uint32_t n = (uint32_t)c.n;
-  for (int64_t it = blockIdx.x; it < reps; it += gridDim.x) {
-    const uint32_t rep = hk.rep_begin + (uint32_t)it;
-    DD sP{0, 0}, sT{0, 0}, sT2{0, 0}, sU{0, 0}, sU2{0, 0};
-    auto uval = [&](uint32_t cd, double l) {  // real-data-sims.R:222-232
-      // finite dictionary (k_panel_dict) and noise: the product is never NaN
-      return rclip_fin((dS[cd & 255u] + c.bs * l) * dO[cd >> 8], c.lr);
-    };
-    auto uterm = [&](double Uc) {
-      ks_acc(sU, Uc);
-      ks_acc(sU2, Uc * Uc);
-    };
-    // a pair of INT terms (of NI batches) is added plainly and the pair sum compensated: half
-    // the TwoSum chains of per-term sums
-    auto uterm2 = [&](double U0, double U1) {
-      ks_acc(sU, U0 + U1);
-      ks_acc(sU2, U0 * U0 + U1 * U1);
-    };
-    // Phase A: the panel codes at the permuted batch slots, gs[t] = code[P(t)], t < k m, into
-    // this workgroup's scratch row (L2-resident, reused by every replicate of the workgroup).
-    // Each lane walks its strided run of t and moves to the next t as soon as a walk lands,
-    // so lanes stay busy while walk lengths differ.  Phase B reads the row after a barrier.
-    const U4 kk = draw(0u, rep, DCOR_SITE_PERM, hk.ni0, hk.ni1);
-    uint16_t* __restrict__ gs = scr + (int64_t)blockIdx.x * scr_stride;
-    {
-      const uint32_t km = (uint32_t)(c.k * c.m);
-      uint32_t t = (uint32_t)tid, x = t;
-      while (t < km) {
-        x = feistel_pass(x, hk.pa, hk.pc, kk);
-        if (x < n) {
-          gs[t] = cod[x];
-          t += DICT_NT;
-          x = t;
-        }
+  DD sP{0, 0}, sT{0, 0}, sT2{0, 0}, sU{0, 0}, sU2{0, 0};
+  auto uval = [&](double2 v, double l) {  // real-data-sims.R:222-232
+    return rclip((v.x + c.bs * l) * v.y, c.lr);
+  };
+  auto uterm = [&](double Uc) {
+    ks_acc(sU, Uc);
+    ks_acc(sU2, Uc * Uc);
+  };
+  auto uterm2 = [&](double U0, double U1) {  // as k_hrs_fused: pair sums compensated
+    ks_acc(sU, U0 + U1);
+    ks_acc(sU2, U0 * U0 + U1 * U1);
+  };
+  // Phase A: gs[t] = P(t), t < k m (sample.int(n, k*m) - 1, real-data-sims.R:131); the
+  // previous item's readers are past the barrier that ends its reduction.
+  const U4 kk = draw(0u, rep, DCOR_SITE_PERM, hk.ni0, hk.ni1);
+  {
+    const uint32_t km = (uint32_t)(c.k * c.m);
+    uint32_t t = (uint32_t)tid, x = t;
+    while (t < km) {
+      x = feistel_pass(x, hk.pa, hk.pc, kk);
+      if (x < n) {
+        gs[t] = (uint16_t)x;
+        t += DICT_NT;
+        x = t;
       }
     }
-    {  // INT local noise: block b -> samples 2b, 2b+1
-      const int64_t nb = c.n >> 1;
-      for (int64_t b = tid; b < nb; b += DICT_NT) {
-        const U4 w = draw((uint32_t)b, rep, HRS_SITE_LOCAL, hk.in0, hk.in1);
-        uterm2(uval(cod[2 * b], unit_laplace(u53(w.w0, w.w1))),
-               uval(cod[2 * b + 1], unit_laplace(u53(w.w2, w.w3))));
-      }
-      if ((c.n & 1) && tid == DICT_NT - 1) {
-        const U4 w = draw((uint32_t)nb, rep, HRS_SITE_LOCAL, hk.in0, hk.in1);
-        uterm(uval(cod[c.n - 1], unit_laplace(u53(w.w0, w.w1))));
+  }
+  {  // INT local noise: block b -> samples 2b, 2b+1
+    const int64_t nb = c.n >> 1;
+    for (int64_t b = tid; b < nb; b += DICT_NT) {
+      const U4 w = draw((uint32_t)b, rep, HRS_SITE_LOCAL, hk.in0, hk.in1);
+      const double2 v0 = so[2 * b], v1 = so[2 * b + 1];
+      uterm2(uval(v0, unit_laplace(u53(w.w0, w.w1))), uval(v1, unit_laplace(u53(w.w2, w.w3))));
+    }
+    if ((c.n & 1) && tid == DICT_NT - 1) {
+      const U4 w = draw((uint32_t)nb, rep, HRS_SITE_LOCAL, hk.in0, hk.in1);
+      uterm(uval(so[c.n - 1], unit_laplace(u53(w.w0, w.w1))));
+    }
+  }
+  double* rb = red + (par & 1) * (10 * DICT_NW);
+  auto wave_put = [&](int v, DD a) {
+    a = wave_sum_dd(a);
+    if ((tid & 63) == 0) {
+      rb[(2 * v) * DICT_NW + (tid >> 6)] = a.hi;
+      rb[(2 * v + 1) * DICT_NW + (tid >> 6)] = a.lo;
+    }
+  };
+  wave_put(3, sU);
+  wave_put(4, sU2);
+  __syncthreads();  // phase A's index row is complete
+  auto nterm = [&](double xt, double yt) {  // real-data-sims.R:133-137
+    ks_acc(sP, xt * yt);
+    const double T = c.md * xt * yt;
+    ks_acc(sT, T);
+    ks_acc(sT2, T * T);
+  };
+  auto nterm2 = [&](double xt0, double yt0, double xt1, double yt1) {
+    const double T0 = c.md * xt0 * yt0, T1 = c.md * xt1 * yt1;
+    ks_acc(sP, xt0 * yt0 + xt1 * yt1);
+    ks_acc(sT, T0 + T1);
+    ks_acc(sT2, T0 * T0 + T1 * T1);
+  };
+  if (c.m == 2) {
+    const uint32_t* __restrict__ g2 = reinterpret_cast<const uint32_t*>(gs);
+    for (int64_t q = tid; 2 * q < c.k; q += DICT_NT) {
+      const uint32_t ab0 = g2[2 * q];
+      const uint32_t ab1 = 2 * q + 1 < c.k ? g2[2 * q + 1] : 0u;
+      const U4 wx = draw((uint32_t)q, rep, HRS_SITE_NI_X, hk.ni0, hk.ni1);
+      const U4 wy = draw((uint32_t)q, rep, HRS_SITE_NI_Y, hk.ni0, hk.ni1);
+      const double2 a0 = xy[ab0 & 0xFFFFu], b0 = xy[ab0 >> 16];
+      const double xt0 = (a0.x + b0.x) * 0.5 + c.bx * unit_laplace(u53(wx.w0, wx.w1));
+      const double yt0 = (a0.y + b0.y) * 0.5 + c.by * unit_laplace(u53(wy.w0, wy.w1));
+      if (2 * q + 1 < c.k) {
+        const double2 a1 = xy[ab1 & 0xFFFFu], b1 = xy[ab1 >> 16];
+        nterm2(xt0, yt0, (a1.x + b1.x) * 0.5 + c.bx * unit_laplace(u53(wx.w2, wx.w3)),
+               (a1.y + b1.y) * 0.5 + c.by * unit_laplace(u53(wy.w2, wy.w3)));
+      } else {
+        nterm(xt0, yt0);
       }
     }
-    double* rb = red + (((it - blockIdx.x) / gridDim.x) & 1) * (10 * DICT_NW);
-    auto wave_put = [&](int v, DD a) {
-      a = wave_sum_dd(a);
-      if ((tid & 63) == 0) {
-        rb[(2 * v) * DICT_NW + (tid >> 6)] = a.hi;
-        rb[(2 * v + 1) * DICT_NW + (tid >> 6)] = a.lo;
+  } else {
+    for (int64_t j = tid; j < c.k; j += DICT_NT) {
+      const U4 wx = draw((uint32_t)(j >> 1), rep, HRS_SITE_NI_X, hk.ni0, hk.ni1);
+      const U4 wy = draw((uint32_t)(j >> 1), rep, HRS_SITE_NI_Y, hk.ni0, hk.ni1);
+      const double lxj = unit_laplace((j & 1) ? u53(wx.w2, wx.w3) : u53(wx.w0, wx.w1));
+      const double lyj = unit_laplace((j & 1) ? u53(wy.w2, wy.w3) : u53(wy.w0, wy.w1));
+      DD bx{0, 0}, by{0, 0};
+      for (int r = 0; r < c.m; ++r) {
+        const double2 v = xy[gs[j * c.m + r]];
+        dd_acc(bx, v.x);
+        dd_acc(by, v.y);
       }
-    };
-    wave_put(3, sU);
-    wave_put(4, sU2);
-    __syncthreads();  // phase A's scratch row is complete
-    auto nterm = [&](double xt, double yt) {  // real-data-sims.R:133-137
-      ks_acc(sP, xt * yt);
-      const double T = c.md * xt * yt;
-      ks_acc(sT, T);
-      ks_acc(sT2, T * T);
-    };
-    auto nterm2 = [&](double xt0, double yt0, double xt1, double yt1) {
-      const double T0 = c.md * xt0 * yt0, T1 = c.md * xt1 * yt1;
-      ks_acc(sP, xt0 * yt0 + xt1 * yt1);
-      ks_acc(sT, T0 + T1);
-      ks_acc(sT2, T0 * T0 + T1 * T1);
-    };
-    if (c.m == 2) {  // batches 2q, 2q+1 share one Philox block of X noise and one of Y noise
-      const uint32_t* __restrict__ g2 = reinterpret_cast<const uint32_t*>(gs);  // batch j's codes
-      auto xt_of = [&](uint32_t ab, double lxj) {
-        return (dX[(ab & 0xFFFFu) & 255u] + dX[(ab >> 16) & 255u]) * 0.5 + c.bx * lxj;
-      };
-      auto yt_of = [&](uint32_t ab, double lyj) {
-        return (dY[(ab & 0xFFFFu) >> 8] + dY[(ab >> 16) >> 8]) * 0.5 + c.by * lyj;
-      };
-      for (int64_t q = tid; 2 * q < c.k; q += DICT_NT) {
-        const U4 wx = draw((uint32_t)q, rep, HRS_SITE_NI_X, hk.ni0, hk.ni1);
-        const U4 wy = draw((uint32_t)q, rep, HRS_SITE_NI_Y, hk.ni0, hk.ni1);
-        const uint32_t ab0 = g2[2 * q];
-        const double xt0 = xt_of(ab0, unit_laplace(u53(wx.w0, wx.w1)));
-        const double yt0 = yt_of(ab0, unit_laplace(u53(wy.w0, wy.w1)));
-        if (2 * q + 1 < c.k) {
-          const uint32_t ab1 = g2[2 * q + 1];
-          nterm2(xt0, yt0, xt_of(ab1, unit_laplace(u53(wx.w2, wx.w3))),
-                 yt_of(ab1, unit_laplace(u53(wy.w2, wy.w3))));
-        } else {
-          nterm(xt0, yt0);
-        }
-      }
-    } else {
-      for (int64_t j = tid; j < c.k; j += DICT_NT) {
-        const U4 wx = draw((uint32_t)(j >> 1), rep, HRS_SITE_NI_X, hk.ni0, hk.ni1);
-        const U4 wy = draw((uint32_t)(j >> 1), rep, HRS_SITE_NI_Y, hk.ni0, hk.ni1);
-        const double lxj = unit_laplace((j & 1) ? u53(wx.w2, wx.w3) : u53(wx.w0, wx.w1));
-        const double lyj = unit_laplace((j & 1) ? u53(wy.w2, wy.w3) : u53(wy.w0, wy.w1));
-        DD bx{0, 0}, by{0, 0};
-        for (int r = 0; r < c.m; ++r) {
-          const uint32_t a = gs[j * c.m + r];
-          dd_acc(bx, dX[a & 255u]);
-          dd_acc(by, dY[a >> 8]);
-        }
-        const DD xb = dd_div_d(bx, c.md), yb = dd_div_d(by, c.md);
-        nterm((xb.hi + xb.lo) + c.bx * lxj, (yb.hi + yb.lo) + c.by * lyj);
-      }
+      const DD xb = dd_div_d(bx, c.md), yb = dd_div_d(by, c.md);
+      nterm((xb.hi + xb.lo) + c.bx * lxj, (yb.hi + yb.lo) + c.by * lyj);
     }
-    wave_put(0, sP);
-    wave_put(1, sT);
-    wave_put(2, sT2);
-    __syncthreads();
-    if (tid < 5) {
-      const DD a = fold_waves_dd<DICT_NW>(rb + (2 * tid) * DICT_NW, rb + (2 * tid + 1) * DICT_NW);
-      part[it].s[2 * tid] = a.hi;
-      part[it].s[2 * tid + 1] = a.lo;
-    }
+  }
+  wave_put(0, sP);
+  wave_put(1, sT);
+  wave_put(2, sT2);
+  __syncthreads();
+  if (tid < 5) {
+    const DD a = fold_waves_dd<DICT_NW>(rb + (2 * tid) * DICT_NW, rb + (2 * tid + 1) * DICT_NW);
+    dst->s[2 * tid] = a.hi;
+    dst->s[2 * tid + 1] = a.lo;
   }
 }
 
@@ -1704,131 +1853,23 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_fused_l2(PrematSubgConst p
                                                               int64_t reps,
                                                               SubgPartial* __restrict__ part) {
   extern __shared__ double dsm[];
-  const SubgConst& c = p.s;
-  const int tid = threadIdx.x;
   double* red = dsm;
   uint16_t* gs = reinterpret_cast<uint16_t*>(dsm + 20 * DICT_NW);
-  const double2* __restrict__ xy = p.xyc;
-  const double2* __restrict__ so = p.soc;
-  const uint32_t n = (uint32_t)c.n;
   for (int64_t it = blockIdx.x; it < reps; it += gridDim.x) {
-    const uint32_t rep = hk.rep_begin + (uint32_t)it;
-    DD sP{0, 0}, sT{0, 0}, sT2{0, 0}, sU{0, 0}, sU2{0, 0};
-    auto uval = [&](double2 v, double l) {  // real-data-sims.R:222-232
-      return rclip((v.x + c.bs * l) * v.y, c.lr);
-    };
-    auto uterm = [&](double Uc) {
-      ks_acc(sU, Uc);
-      ks_acc(sU2, Uc * Uc);
-    };
-    auto uterm2 = [&](double U0, double U1) {  // as k_hrs_fused: pair sums compensated
-      ks_acc(sU, U0 + U1);
-      ks_acc(sU2, U0 * U0 + U1 * U1);
-    };
-    // Phase A: gs[t] = P(t), t < k m (sample.int(n, k*m) - 1, real-data-sims.R:131); the
-    // previous item's readers are past the barrier that ends its reduction.
-    const U4 kk = draw(0u, rep, DCOR_SITE_PERM, hk.ni0, hk.ni1);
-    {
-      const uint32_t km = (uint32_t)(c.k * c.m);
-      uint32_t t = (uint32_t)tid, x = t;
-      while (t < km) {
-        x = feistel_pass(x, hk.pa, hk.pc, kk);
-        if (x < n) {
-          gs[t] = (uint16_t)x;
-          t += DICT_NT;
-          x = t;
-        }
-      }
-    }
-    {  // INT local noise: block b -> samples 2b, 2b+1
-      const int64_t nb = c.n >> 1;
-      for (int64_t b = tid; b < nb; b += DICT_NT) {
-        const U4 w = draw((uint32_t)b, rep, HRS_SITE_LOCAL, hk.in0, hk.in1);
-        const double2 v0 = so[2 * b], v1 = so[2 * b + 1];
-        uterm2(uval(v0, unit_laplace(u53(w.w0, w.w1))), uval(v1, unit_laplace(u53(w.w2, w.w3))));
-      }
-      if ((c.n & 1) && tid == DICT_NT - 1) {
-        const U4 w = draw((uint32_t)nb, rep, HRS_SITE_LOCAL, hk.in0, hk.in1);
-        uterm(uval(so[c.n - 1], unit_laplace(u53(w.w0, w.w1))));
-      }
-    }
-    double* rb = red + (((it - blockIdx.x) / gridDim.x) & 1) * (10 * DICT_NW);
-    auto wave_put = [&](int v, DD a) {
-      a = wave_sum_dd(a);
-      if ((tid & 63) == 0) {
-        rb[(2 * v) * DICT_NW + (tid >> 6)] = a.hi;
-        rb[(2 * v + 1) * DICT_NW + (tid >> 6)] = a.lo;
-      }
-    };
-    wave_put(3, sU);
-    wave_put(4, sU2);
-    __syncthreads();  // phase A's index row is complete
-    auto nterm = [&](double xt, double yt) {  // real-data-sims.R:133-137
-      ks_acc(sP, xt * yt);
-      const double T = c.md * xt * yt;
-      ks_acc(sT, T);
-      ks_acc(sT2, T * T);
-    };
-    auto nterm2 = [&](double xt0, double yt0, double xt1, double yt1) {
-      const double T0 = c.md * xt0 * yt0, T1 = c.md * xt1 * yt1;
-      ks_acc(sP, xt0 * yt0 + xt1 * yt1);
-      ks_acc(sT, T0 + T1);
-      ks_acc(sT2, T0 * T0 + T1 * T1);
-    };
-    if (c.m == 2) {
-      const uint32_t* __restrict__ g2 = reinterpret_cast<const uint32_t*>(gs);
-      for (int64_t q = tid; 2 * q < c.k; q += DICT_NT) {
-        const uint32_t ab0 = g2[2 * q];
-        const uint32_t ab1 = 2 * q + 1 < c.k ? g2[2 * q + 1] : 0u;
-        const U4 wx = draw((uint32_t)q, rep, HRS_SITE_NI_X, hk.ni0, hk.ni1);
-        const U4 wy = draw((uint32_t)q, rep, HRS_SITE_NI_Y, hk.ni0, hk.ni1);
-        const double2 a0 = xy[ab0 & 0xFFFFu], b0 = xy[ab0 >> 16];
-        const double xt0 = (a0.x + b0.x) * 0.5 + c.bx * unit_laplace(u53(wx.w0, wx.w1));
-        const double yt0 = (a0.y + b0.y) * 0.5 + c.by * unit_laplace(u53(wy.w0, wy.w1));
-        if (2 * q + 1 < c.k) {
-          const double2 a1 = xy[ab1 & 0xFFFFu], b1 = xy[ab1 >> 16];
-          nterm2(xt0, yt0, (a1.x + b1.x) * 0.5 + c.bx * unit_laplace(u53(wx.w2, wx.w3)),
-                 (a1.y + b1.y) * 0.5 + c.by * unit_laplace(u53(wy.w2, wy.w3)));
-        } else {
-          nterm(xt0, yt0);
-        }
-      }
-    } else {
-      for (int64_t j = tid; j < c.k; j += DICT_NT) {
-        const U4 wx = draw((uint32_t)(j >> 1), rep, HRS_SITE_NI_X, hk.ni0, hk.ni1);
-        const U4 wy = draw((uint32_t)(j >> 1), rep, HRS_SITE_NI_Y, hk.ni0, hk.ni1);
-        const double lxj = unit_laplace((j & 1) ? u53(wx.w2, wx.w3) : u53(wx.w0, wx.w1));
-        const double lyj = unit_laplace((j & 1) ? u53(wy.w2, wy.w3) : u53(wy.w0, wy.w1));
-        DD bx{0, 0}, by{0, 0};
-        for (int r = 0; r < c.m; ++r) {
-          const double2 v = xy[gs[j * c.m + r]];
-          dd_acc(bx, v.x);
-          dd_acc(by, v.y);
-        }
-        const DD xb = dd_div_d(bx, c.md), yb = dd_div_d(by, c.md);
-        nterm((xb.hi + xb.lo) + c.bx * lxj, (yb.hi + yb.lo) + c.by * lyj);
-      }
-    }
-    wave_put(0, sP);
-    wave_put(1, sT);
-    wave_put(2, sT2);
-    __syncthreads();
-    if (tid < 5) {
-      const DD a = fold_waves_dd<DICT_NW>(rb + (2 * tid) * DICT_NW, rb + (2 * tid + 1) * DICT_NW);
-      part[it].s[2 * tid] = a.hi;
-      part[it].s[2 * tid + 1] = a.lo;
-    }
+    hrs_fused_l2_item(p, hk, hk.rep_begin + (uint32_t)it, gs,
+                      red, (int)((it - blockIdx.x) / gridDim.x), part + it);
   }
 }
 
 // Epilogue of k_hrs_fused: central Laplace and mixquant draws generated here.  Thread t holds
 // the pairs of Philox blocks t + 256 s (order is irrelevant to an order statistic).
-__global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_fused_epilogue(PrematSubgConst p, HrsKeys hk,
-                                                                   const SubgPartial* __restrict__ part,
-                                                                   dcor_rep_out* out) {
-  __shared__ SelScratch sel;
-  const int64_t r = blockIdx.x;
-  const uint32_t rep = hk.rep_begin + (uint32_t)r;
+// Item r of the launch (its partial sums part[r]) is replicate `rep` under constants p and keys
+// hk; the record goes to *dst.  sel / bc: the workgroup's static LDS.
+__device__ __forceinline__ void hrs_fused_epilogue_item(const PrematSubgConst& p, const HrsKeys& hk,
+                                                        uint32_t rep, int64_t r,
+                                                        const SubgPartial* __restrict__ part,
+                                                        dcor_rep_out* dst, SelScratch& sel,
+                                                        double (&bc)[2]) {
   const MixConst& mx = p.s.mix;
   double zv[SEL_VPT], lv[SEL_VPT];
   bool have[SEL_VPT];
@@ -1847,7 +1888,6 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_fused_epilogue(PrematSubgCon
     }
   }
   // the scalar half in wave 0 only (as k_premat_subg_epilogue); c* reaches the others through LDS
-  __shared__ double bc[2];
   SubgPre pre{};
   if (threadIdx.x < 64) {
     const U4 wc = draw(0u, rep, HRS_SITE_CENTRAL, hk.in0, hk.in1);
@@ -1874,7 +1914,122 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_fused_epilogue(PrematSubgCon
     __syncthreads();
     qq = value_select(val, mx.pos, mx.nsim - sel.nan_cnt, &sel);
   }
-  if (threadIdx.x == 0) out[r] = premat_subg_post(p, pre, qq);
+  if (threadIdx.x == 0) *dst = premat_subg_post(p, pre, qq);
+}
+
+__global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_fused_epilogue(PrematSubgConst p, HrsKeys hk,
+                                                                   const SubgPartial* __restrict__ part,
+                                                                   dcor_rep_out* out) {
+  __shared__ SelScratch sel;
+  __shared__ double bc[2];
+  const int64_t r = blockIdx.x;
+  hrs_fused_epilogue_item(p, hk, hk.rep_begin + (uint32_t)r, r, part, out + r, sel, bc);
+}
+
+// ------------------------------------------- fused HRS sweep: every eps in one launch ---
+// k_hrs_fused / k_hrs_fused_l2 / k_hrs_fused_epilogue over the replicates of several segments
+// (one eps, key pair and replicate range each: real-data-sims.R:345-448's loop over eps_grid):
+// work item i is a replicate of the segment whose [first, first + reps) holds i, and that
+// segment's constants come from a device table (HrsSegConst) instead of the launch arguments.
+// The replicate itself is hrs_fused_item / hrs_fused_l2_item / hrs_fused_epilogue_item, so every
+// record equals the per-segment launch's bit for bit.  The table is read through the constant
+// address space at workgroup-uniform addresses: scalar loads into SGPRs, once per segment a
+// workgroup enters, never per lane and never inside the replicate's loops.
+typedef const __attribute__((address_space(4))) HrsSegConst* HrsSegTab;
+
+// The last segment whose first item is <= it (`first` is strictly increasing, tab[0].first = 0).
+__device__ __forceinline__ int hrs_seg_find(HrsSegTab tab, int nseg, int64_t it) {
+  int lo = 0, hi = nseg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].first <= it) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// Segment s's constants over the sweep-wide ones in p, its keys into hk.
+__device__ __forceinline__ void hrs_seg_load(HrsSegTab tab, int s, PrematSubgConst& p, HrsKeys& hk) {
+  SubgConst& c = p.s;
+  c.k = tab[s].k; c.m = tab[s].m; c.md_pow2 = tab[s].md_pow2;
+  c.md = tab[s].md; c.kd = tab[s].kd; c.inv_md = tab[s].inv_md;
+  c.bx = tab[s].bx; c.by = tab[s].by; c.m_over_k = tab[s].m_over_k; c.sqrt_k = tab[s].sqrt_k;
+  c.lr = tab[s].lr; c.bs = tab[s].bs; c.s_central = tab[s].s_central; c.sn2x2 = tab[s].sn2x2;
+  c.eps_r = tab[s].eps_r; p.crit_sqrt2_s = tab[s].crit_sqrt2_s;
+  hk.ni0 = tab[s].ni0; hk.ni1 = tab[s].ni1; hk.in0 = tab[s].in0; hk.in1 = tab[s].in1;
+  hk.rep_begin = tab[s].rep_begin;
+}
+
+// A workgroup's items ascend, so it re-reads the table only when an item passes the end of the
+// segment it holds.
+struct HrsSegCursor {
+  int64_t first = 0, end = 0;   // items [first, end) belong to the loaded segment
+  __device__ __forceinline__ void seek(HrsSegTab tab, int nseg, int64_t items, int64_t it,
+                                       PrematSubgConst& p, HrsKeys& hk) {
+    if (it < end) return;
+    const int s = __builtin_amdgcn_readfirstlane(hrs_seg_find(tab, nseg, it));
+    hrs_seg_load(tab, s, p, hk);
+    first = tab[s].first;
+    end = s + 1 < nseg ? tab[s + 1].first : items;
+  }
+};
+
+template <int WPE>
+__global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_sweep_fused(PrematSubgConst p, int pa, int pc,
+                                                                 const HrsSegConst* __restrict__ tab_g,
+                                                                 int nseg,
+                                                                 const uint16_t* __restrict__ codes_g,
+                                                                 const double* __restrict__ dict_g,
+                                                                 int64_t items,
+                                                                 SubgPartial* __restrict__ part,
+                                                                 uint16_t* __restrict__ scr,
+                                                                 int64_t scr_stride) {
+  extern __shared__ double dsm[];
+  const HrsLds L = hrs_fused_setup(p, codes_g, dict_g, dsm);
+  const HrsSegTab tab = (HrsSegTab)tab_g;
+  HrsKeys hk{0, 0, 0, 0, 0, pa, pc};
+  HrsSegCursor cur;
+  int par = 0;
+  for (int64_t it = blockIdx.x; it < items; it += gridDim.x, par ^= 1) {
+    cur.seek(tab, nseg, items, it, p, hk);
+    hrs_fused_item(p, hk, hk.rep_begin + (uint32_t)(it - cur.first), L.dX, L.dY, L.dS, L.dO, L.cod,
+                   scr + (int64_t)blockIdx.x * scr_stride, L.red, par, part + it);
+  }
+}
+
+template <int WPE>
+__global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_sweep_fused_l2(PrematSubgConst p, int pa, int pc,
+                                                                    const HrsSegConst* __restrict__ tab_g,
+                                                                    int nseg, int64_t items,
+                                                                    SubgPartial* __restrict__ part) {
+  extern __shared__ double dsm[];
+  double* red = dsm;
+  uint16_t* gs = reinterpret_cast<uint16_t*>(dsm + 20 * DICT_NW);  // the largest k m of the segments
+  const HrsSegTab tab = (HrsSegTab)tab_g;
+  HrsKeys hk{0, 0, 0, 0, 0, pa, pc};
+  HrsSegCursor cur;
+  int par = 0;
+  for (int64_t it = blockIdx.x; it < items; it += gridDim.x, par ^= 1) {
+    cur.seek(tab, nseg, items, it, p, hk);
+    hrs_fused_l2_item(p, hk, hk.rep_begin + (uint32_t)(it - cur.first), gs,
+                      red, par, part + it);
+  }
+}
+
+// One epilogue launch over all items: block r finds its segment.
+__global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_sweep_fused_epilogue(PrematSubgConst p,
+                                                                         const HrsSegConst* __restrict__ tab_g,
+                                                                         int nseg,
+                                                                         const SubgPartial* __restrict__ part,
+                                                                         dcor_rep_out* out) {
+  __shared__ SelScratch sel;
+  __shared__ double bc[2];
+  const HrsSegTab tab = (HrsSegTab)tab_g;
+  const int64_t r = blockIdx.x;
+  HrsKeys hk{0, 0, 0, 0, 0, 0, 0};   // the epilogue draws no permutation: pa, pc unused
+  const int s = __builtin_amdgcn_readfirstlane(hrs_seg_find(tab, nseg, r));
+  hrs_seg_load(tab, s, p, hk);
+  const int64_t j = r - tab[s].first;
+  hrs_fused_epilogue_item(p, hk, hk.rep_begin + (uint32_t)j, r, part, out + tab[s].out_row + j, sel, bc);
 }
 
 // ============================================================ launchers ===
@@ -1900,6 +2055,13 @@ static int persistent_grid(const void* kernel, int threads, size_t lds, int64_t 
   return 0;
 }
 
+// The Feistel split of ceil(log2 n) bits (launch_perm's).
+static void hrs_feistel_split(int64_t n, int* pa, int* pc) {
+  int bits = 1;
+  while ((1ll << bits) < n) ++bits;
+  *pa = bits / 2; *pc = bits - *pa;
+}
+
 int launch_hrs_fused(const PrematSubgConst& c, uint64_t seed_ni, uint64_t seed_int,
                      int64_t rep_begin, int64_t reps, void* part, dcor_rep_out* out,
                      void* stream) {
@@ -1908,9 +2070,7 @@ int launch_hrs_fused(const PrematSubgConst& c, uint64_t seed_ni, uint64_t seed_i
   hk.ni0 = (uint32_t)seed_ni; hk.ni1 = (uint32_t)(seed_ni >> 32);
   hk.in0 = (uint32_t)seed_int; hk.in1 = (uint32_t)(seed_int >> 32);
   hk.rep_begin = (uint32_t)rep_begin;
-  int bits = 1;
-  while ((1ll << bits) < c.s.n) ++bits;
-  hk.pa = bits / 2; hk.pc = bits - hk.pa;
+  hrs_feistel_split(c.s.n, &hk.pa, &hk.pc);
   const int wsel = (int)dcor::variant("DCOR_HRS_WPE").as_int(6, 4, 4);
   const bool l2 = c.xyc != nullptr;  // uncoded panel: packed clips in HBM, indices in LDS
   const size_t lds = l2 ? (size_t)(20 * DICT_NW) * sizeof(double) +
@@ -1945,6 +2105,45 @@ int launch_hrs_fused(const PrematSubgConst& c, uint64_t seed_ni, uint64_t seed_i
   (void)hipFreeAsync(scr, (hipStream_t)stream);
   hipLaunchKernelGGL(k_hrs_fused_epilogue, dim3((unsigned)reps), dim3(DCOR_BLOCK), 0,
                      (hipStream_t)stream, c, hk, (const SubgPartial*)part, out);
+  return (int)hipGetLastError();
+}
+
+int launch_hrs_fused_sweep(const PrematSubgConst& c, const HrsSegConst* tab, int nseg, int64_t items,
+                           int64_t max_km, void* part, dcor_rep_out* out, void* stream) {
+  if (items <= 0 || nseg <= 0) return 0;
+  int pa, pc;
+  hrs_feistel_split(c.s.n, &pa, &pc);
+  const int wsel = (int)dcor::variant("DCOR_HRS_WPE").as_int(6, 4, 4);
+  const bool l2 = c.xyc != nullptr;  // uncoded panel: packed clips in HBM, indices in LDS
+  const size_t lds = l2 ? (size_t)(20 * DICT_NW) * sizeof(double) + (size_t)((max_km * 2 + 15) / 16) * 16
+                        : premat_dict_lds_bytes(c.s.n);
+  if (l2)   // the clips are sweep-wide: once per call
+    hipLaunchKernelGGL(k_premat_xy_pack, dim3((unsigned)((c.s.n + DCOR_BLOCK - 1) / DCOR_BLOCK)),
+                       dim3(DCOR_BLOCK), 0, (hipStream_t)stream, c, (double2*)c.xyc,
+                       (double2*)c.soc);
+  typedef void (*SweepK)(PrematSubgConst, int, int, const HrsSegConst*, int, const uint16_t*,
+                         const double*, int64_t, SubgPartial*, uint16_t*, int64_t);
+  typedef void (*SweepL2K)(PrematSubgConst, int, int, const HrsSegConst*, int, int64_t, SubgPartial*);
+  const SweepK kern = wsel == 4 ? k_hrs_sweep_fused<4> : k_hrs_sweep_fused<6>;
+  const SweepL2K kern_l2 = wsel == 4 ? k_hrs_sweep_fused_l2<4> : k_hrs_sweep_fused_l2<6>;
+  const void* kf = l2 ? (const void*)kern_l2 : (const void*)kern;
+  int64_t grid = 0;
+  if (int e = persistent_grid(kf, DICT_NT, lds, items, &grid, kLdsDynMax)) return e;
+  void* scr = nullptr;
+  if (l2) {
+    hipLaunchKernelGGL(kern_l2, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c, pa,
+                       pc, tab, nseg, items, (SubgPartial*)part);
+  } else {
+    const int64_t stride = (max_km + 63) & ~(int64_t)63;  // u16 codes per scratch row
+    if (hipMallocAsync(&scr, (size_t)(grid * stride * 2), (hipStream_t)stream) != hipSuccess)
+      return (int)hipGetLastError();
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c, pa, pc,
+                       tab, nseg, c.dict_codes, c.dict_vals, items, (SubgPartial*)part,
+                       (uint16_t*)scr, stride);
+    (void)hipFreeAsync(scr, (hipStream_t)stream);
+  }
+  hipLaunchKernelGGL(k_hrs_sweep_fused_epilogue, dim3((unsigned)items), dim3(DCOR_BLOCK), 0,
+                     (hipStream_t)stream, c, tab, nseg, (const SubgPartial*)part, out);
   return (int)hipGetLastError();
 }
 

@@ -152,6 +152,8 @@ SIGNATURES = {
                                         C.c_int64, _P, _P]),
     "dcor_hrs_sweep_launch": (C.c_int, [C.POINTER(PrematSubg), _P, C.POINTER(HrsSegment), C.c_int64,
                                         _P, _P]),
+    "dcor_hrs_fused_sweep_launch": (C.c_int, [C.POINTER(PrematSubg), _P, C.POINTER(HrsSegment), C.c_int64,
+                                              _P, _P]),
     "dcor_batch_geometry": (C.c_int, [C.c_int64, C.c_double, C.c_double, C.c_int, C.c_int, _I64]),
     "dcor_ci_ni_signbatch": (C.c_int, [_D, _D, C.c_int64, C.c_double, C.c_double, C.c_double,
                                        C.c_int, _D, _D, _D, _D]),

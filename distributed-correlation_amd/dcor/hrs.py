@@ -225,10 +225,12 @@ def _summ(method, eps, hat, lo, hi) -> dict:
             "ci_low_q10": q(lo, 0.10), "ci_high_q90": q(hi, 0.90)}
 
 
-def _native_segments(X, Y, pn, lam_age, lam_bmi, nsim, alpha, rowsegs, out, stream):
+def _native_segments(X, Y, pn, lam_age, lam_bmi, nsim, alpha, rowsegs, out, stream, mode="premat"):
     """Enqueue (eps, seed_ni, seed_int, first run, count, output row) segments on `stream` with one
     dcor_hrs_sweep_launch: per segment the seven Philox noise arrays in one launch, then the
-    pre-materialised panel kernels, records to out[row ..]."""
+    pre-materialised panel kernels, records to out[row ..].  mode='fused': one
+    dcor_hrs_fused_sweep_launch instead -- every segment in one launch of the in-kernel-noise
+    kernels, no noise arrays."""
     import ctypes as C
 
     from . import _lib
@@ -241,8 +243,9 @@ def _native_segments(X, Y, pn, lam_age, lam_bmi, nsim, alpha, rowsegs, out, stre
     arr = (_lib.HrsSegment * len(rowsegs))(*[
         _lib.HrsSegment(eps=e, seed_ni=sn, seed_int=si, rep_begin=r0, reps=c, out_row=row)
         for e, sn, si, r0, c, row in rowsegs])
-    _lib.check(_lib.lib.dcor_hrs_sweep_launch(C.byref(base), pn, arr, len(rowsegs),
-                                              C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)))
+    launch = _lib.lib.dcor_hrs_fused_sweep_launch if mode == "fused" else _lib.lib.dcor_hrs_sweep_launch
+    _lib.check(launch(C.byref(base), pn, arr, len(rowsegs), C.c_void_p(out.data_ptr()),
+                      C.c_void_p(stream.cuda_stream)))
 
 
 _SIDE = {}
@@ -259,7 +262,18 @@ def _side_streams(ns):
     return pool[:ns]
 
 
-def sweep_segments(age_z, bmi_z, lam_age, lam_bmi, eps_grid, segs, nsim=2000, alpha=0.05, streams=1):
+def _check_sweep_mode(mode, rng, streams):
+    """The sweeps' mode argument, checked before any device work (as hrs_replicates checks its own)."""
+    if mode not in ("premat", "fused"):
+        raise ValueError(f"mode must be 'premat' or 'fused', not {mode!r}")
+    if mode == "fused" and rng != "philox":
+        raise ValueError("mode='fused' draws Philox noise in the kernel: rng='philox'")
+    if mode == "fused" and streams > 1:
+        raise ValueError("mode='fused' runs every segment in one launch: streams=1")
+
+
+def sweep_segments(age_z, bmi_z, lam_age, lam_bmi, eps_grid, segs, nsim=2000, alpha=0.05, streams=1,
+                   mode="premat"):
     """Philox pre-materialised runs of several (eps index 0-based, first run, count) segments of
     an eps sweep on one shared panel -> [sum(count), 6] float64 in segment order.  Each segment's
     runs equal hrs_replicates(eps_grid[e], count, seed_ni=10 + 1000 idx, seed_int=20 + 1000 idx,
@@ -267,7 +281,13 @@ def sweep_segments(age_z, bmi_z, lam_age, lam_bmi, eps_grid, segs, nsim=2000, al
     uploaded and encoded once and the per-eps launch chains run from one native call
     (dcor_hrs_sweep_launch) instead of eight launches from Python per eps; with streams > 1 the
     segments are dealt round-robin over that many HIP streams, one native call each.  The host
-    waits once, at the end."""
+    waits once, at the end.
+
+    mode='fused' (streams = 1 only) draws the same Philox noise inside the kernels
+    (dcor_hrs_fused_sweep_launch): one streaming launch and one epilogue launch cover every
+    segment, whatever its eps, and no noise array is allocated.  Each segment's runs then equal
+    hrs_replicates(..., mode='fused') with the same keys and rep_begin byte for byte."""
+    _check_sweep_mode(mode, "philox", streams)
     import ctypes as C
 
     import torch
@@ -291,7 +311,7 @@ def sweep_segments(age_z, bmi_z, lam_age, lam_bmi, eps_grid, segs, nsim=2000, al
         for j, s in enumerate(side):
             if s is not main:
                 s.wait_stream(main)              # X, Y, the panel and out exist before any launch
-            _native_segments(X, Y, pn, lam_age, lam_bmi, nsim, alpha, rowsegs[j::ns], out, s)
+            _native_segments(X, Y, pn, lam_age, lam_bmi, nsim, alpha, rowsegs[j::ns], out, s, mode)
         for s in side:
             if s is not main:
                 main.wait_stream(s)
@@ -304,15 +324,19 @@ def sweep_segments(age_z, bmi_z, lam_age, lam_bmi, eps_grid, segs, nsim=2000, al
 
 
 def eps_sweep(age_z, bmi_z, lam_age, lam_bmi, eps_grid=EPS_GRID, reps=R_PER_EPS, nsim=2000,
-              rng="philox", streams=1):
+              rng="philox", streams=1, mode="premat"):
     """The replicate sweep of real-data-sims.R:345-448: for every eps in seq(.25, 2.5, .1),
     `reps` NI and INT runs (Philox keys 10 + 1000 idx and 20 + 1000 idx, idx 1-based as
     which(eps_grid == eps); rng='R': the reference's own per-run set.seed streams) and the
     per-eps summaries ni_mean / int_mean.  rng='philox' runs every eps on one encoded panel from
-    one native call per HIP stream (sweep_segments); the runs equal one hrs_replicates call per eps."""
+    one native call per HIP stream (sweep_segments); the runs equal one hrs_replicates call per eps.
+    mode='fused' (rng='philox', streams=1): the whole sweep in one launch of the in-kernel-noise
+    kernels; the runs equal one hrs_replicates(mode='fused') call per eps."""
+    _check_sweep_mode(mode, rng, streams)
     if rng == "philox":
         segs = [(e, 0, reps) for e in range(len(eps_grid))]
-        runs = sweep_segments(age_z, bmi_z, lam_age, lam_bmi, eps_grid, segs, nsim=nsim, streams=streams)
+        runs = sweep_segments(age_z, bmi_z, lam_age, lam_bmi, eps_grid, segs, nsim=nsim, streams=streams,
+                              mode=mode)
         return sweep_summaries(eps_grid, runs.reshape(len(eps_grid), reps, 6))
     runs = [hrs_replicates(age_z, bmi_z, lam_age, lam_bmi, eps, reps, seed_ni=10 + 1000 * idx,
                            seed_int=20 + 1000 * idx, nsim=nsim, rng=rng, eps_idx=idx)

@@ -356,6 +356,24 @@ int dcor_hrs_sweep_launch(const dcor_premat_subg* base, const dcor_panel* panel,
                           const dcor_hrs_segment* segs, int64_t nseg, dcor_rep_out* d_out,
                           void* stream);
 
+/* The same segments with the noise drawn inside the kernels, every segment in one streaming
+ * launch and one epilogue launch: the record at d_out[out_row + j] of a segment equals record j
+ * of dcor_hrs_fused_launch called with that segment's eps, seeds, rep_begin and reps on the same
+ * panel, bit for bit (the same per-replicate code; a segment's eps-dependent constants come from
+ * a device table instead of the launch arguments).  base and segs as for dcor_hrs_sweep_launch,
+ * and the same checks before anything is enqueued: an invalid sweep returns DCOR_EINVAL and
+ * leaves d_out untouched; nseg == 0 (at once) or no replicates at all returns DCOR_OK with no
+ * device work.
+ * At most 2^31 - 1 replicates per call.  Asynchronous on `stream`; segs is borrowed for the call
+ * only.  Scratch is stream-ordered: 80 B per replicate, the segment table, and the coded
+ * kernel's u16 row per resident workgroup or the uncoded kernel's packed clips (32 B per
+ * sample) -- no noise array.  DCOR_HRS_WPE and DCOR_HRS_FUSED_L2 act as in dcor_hrs_fused_launch.
+ * An uncoded panel with n > 65536, or a base whose clips differ between segments (lam_s / lam_o
+ * NaN), has no sweep kernel: its segments run one by one through dcor_hrs_fused_launch. */
+int dcor_hrs_fused_sweep_launch(const dcor_premat_subg* base, const dcor_panel* panel,
+                                const dcor_hrs_segment* segs, int64_t nseg, dcor_rep_out* d_out,
+                                void* stream);
+
 int dcor_premat_sign_launch(const dcor_premat_sign* d, dcor_rep_out* d_out, void* stream);
 int dcor_premat_subg_launch(const dcor_premat_subg* d, dcor_rep_out* d_out, void* stream);
 
