@@ -433,6 +433,29 @@ def hrs_sweep_fused(R):
               "in-kernel-noise kernels (hrs.sweep_segments(mode='fused')), summaries on the host")
 
 
+def sign_panel(R, big=100_000):
+    """SP: the sign family (ci_NI_signbatch + ci_INT_signflip) on the stand-in panel with every draw
+    made inside the kernel (dcor_sign_panel_launch): the 23 eps x R sweep in one call, and `big`
+    replicates at eps = (1, 1).  Not in the default list: reach it with --only SP."""
+    import numpy as np
+    import torch
+    from dcor import hrs, signpanel
+    X, Y = hrs_panel("coded")[:2]
+    for name, fn, total in (
+            ("SP-sweep", lambda: signpanel.eps_sweep(X, Y, hrs.EPS_GRID, R)["runs"], len(hrs.EPS_GRID) * R),
+            ("SP", lambda: signpanel.replicates(X, Y, 1.0, 1.0, big, seed=1_000_001), big)):
+        fn()    # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = fn()
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        line(name, n=int(len(X)), replicates=total, seconds=t, reps_per_s=total / t,
+             finite=bool(np.isfinite(res[..., [0, 3, 4, 5]]).all()), kernel="k_sign_panel_prep + k_sign_panel",
+             note="host wall time of one call: panel upload, one preparation launch, one replicate launch "
+                  "over every segment, records copied back")
+
+
 def subg():
     from dcor.sim import CellSpec, simulate
     cell = CellSpec(n=100_000, rho=0.5, eps1=1.0, eps2=1.0, family="subG", dgp="bounded_factor", seed=5)
@@ -736,6 +759,7 @@ def main():
     if "C5fc" in which: c5_fused(a.c5e_R, panel="continuous")
     if "HS" in which: hrs_sweep(a.hs_R)
     if "HSf" in which: hrs_sweep_fused(a.hs_R)
+    if "SP" in which: sign_panel(a.hs_R)
     if "S" in which: subg()
     if "R1" in which: rstream_c1()
     if "RG" in which: rstream_grid()

@@ -1455,6 +1455,62 @@ int dcor_hrs_fused_sweep_launch(const dcor_premat_subg* base, const dcor_panel* 
   return DCOR_OK;
 }
 
+int dcor_sign_panel_launch(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs,
+                           int64_t nseg, dcor_rep_out* d_out, void* stream) {
+  if (!p || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
+    return fail(DCOR_EINVAL, "sign_panel: null argument");
+  if (nseg == 0) return DCOR_OK;   // nothing to run
+  if (!p->X || !p->Y) return fail(DCOR_EINVAL, "sign_panel: null argument (X, Y)");
+  // every segment's own fields, then its launch constants (n, eps, alpha, ci_mode, nsim, k >= 1:
+  // make_sign): nothing is enqueued for an invalid call
+  int64_t items = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_sign_segment& g = segs[i];
+    if (g.reps < 0 || g.rep_begin < 0 || g.out_row < 0 || !(g.eps1 > 0.0) || !(g.eps2 > 0.0))
+      return fail(DCOR_EINVAL, "sign_panel: segment %lld: need eps1, eps2 > 0, reps, rep_begin, out_row >= 0",
+                  (long long)i);
+    if (rep_range_exceeds(g.rep_begin, g.reps))
+      return fail(DCOR_EINVAL, "sign_panel: segment %lld: replicate range exceeds 2^32", (long long)i);
+    items += g.reps;   // reps <= 2^32 each: no overflow below 2^31 segments
+    if (items > 0x7fffffffLL)
+      return fail(DCOR_EINVAL, "sign_panel: more than 2^31 - 1 replicates in one call");
+  }
+  std::vector<SignSegConst> tab;
+  int64_t first = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_sign_segment& g = segs[i];
+    SignSegConst t;
+    std::memset(&t, 0, sizeof(t));
+    if (int st = make_sign(p->n, g.eps1, g.eps2, p->alpha, p->normalise, p->ci_mode, p->nsim, false, t.s))
+      return st;
+    if (g.reps == 0) continue;
+    t.s.k0 = (uint32_t)g.seed; t.s.k1 = (uint32_t)(g.seed >> 32);
+    t.s.rep_begin = g.rep_begin;
+    t.first = first; t.out_row = g.out_row;
+    first += g.reps;
+    tab.push_back(t);
+  }
+  if (items == 0) return DCOR_OK;
+  if (int st = need_device()) return st;
+  const SignPanelLayout lay((int64_t)tab.size(), p->n);
+  void* buf = nullptr;
+  const hipStream_t st = (hipStream_t)stream;
+  if (hipMallocAsync(&buf, lay.bytes, st) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(DCOR_ENOMEM, "sign_panel: cannot allocate %zu scratch bytes", lay.bytes);
+  }
+  count_alloc();
+  // from pageable memory: the copy has left `tab` when the call returns
+  int rc = (int)hipMemcpyAsync(lay.tab(buf), tab.data(), tab.size() * sizeof(SignSegConst),
+                               hipMemcpyHostToDevice, st);
+  if (!rc)
+    rc = launch_sign_panel(tab[0].s, p->X, p->Y, lay.means(buf), lay.xyc(buf), lay.tab(buf),
+                           (int)tab.size(), items, d_out, stream);
+  (void)hipFreeAsync(buf, st);
+  if (rc) return hip_fail((hipError_t)rc, "sign_panel launch");
+  return DCOR_OK;
+}
+
 int dcor_panel_dict_probe(const double* d_X, const double* d_Y, int64_t n, int* ok) {
   if (!d_X || !d_Y || !ok || n < 1) return fail(DCOR_EINVAL, "panel_dict_probe: bad arguments");
   if (int st = need_device()) return st;

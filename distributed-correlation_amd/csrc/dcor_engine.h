@@ -343,6 +343,44 @@ static_assert(sizeof(HrsSegConst) == 160, "the sweep's device table stride");
 // out[s.out_row + (i - s.first)].
 int launch_hrs_fused_sweep(const PrematSubgConst& c, const HrsSegConst* tab, int nseg, int64_t items,
                            int64_t max_km, void* part, dcor_rep_out* out, void* stream);
+// The grid of a persistent kernel over `items` work items (dcor_premat.hip): one workgroup per
+// resident slot at `threads` and `lds` dynamic LDS bytes, at most one per item; lds_limit != 0
+// first raises the kernel's dynamic-LDS limit to it.  Returns hipError_t as int.
+int persistent_grid(const void* kernel, int threads, size_t lds, int64_t items, int64_t* grid,
+                    int lds_limit = 0);
+
+// ---- sign family on a shared panel (dcor_sign_panel_launch; dcor_signpanel.hip) ----
+// One segment of a sign-panel call: make_sign's constants for the segment's (eps1, eps2) with its
+// Philox key in s.k0 / s.k1 and its first replicate in s.rep_begin, and its place in the call.
+// The launch's device table holds the segments with reps > 0 in call order, so `first` is strictly
+// increasing.  The kernel reads the fields it needs at workgroup-uniform addresses.
+struct SignSegConst {
+  SignConst s;
+  int64_t first;     // the segment's first work item: the sum of the reps before it
+  int64_t out_row;
+};
+// Sign-panel scratch: head (the four clipped means, 256 B) | the segment table | the packed panel
+// (xc, yc) of n rounded up to a whole 4-sample flip block.  Every region starts 256-B aligned when
+// the base is.
+struct SignPanelLayout {
+  int64_t npad;
+  size_t tab_off, pack_off, bytes;
+  SignPanelLayout(int64_t nseg, int64_t n)
+      : npad((n + 3) & ~(int64_t)3), tab_off(256),
+        pack_off(tab_off + al256((size_t)nseg * sizeof(SignSegConst))),
+        bytes(pack_off + (size_t)npad * 2 * sizeof(double)) {}
+  double* means(void* base) const { return (double*)base; }
+  SignSegConst* tab(void* base) const { return (SignSegConst*)((char*)base + tab_off); }
+  void* xyc(void* base) const { return (char*)base + pack_off; }
+};
+// The preparation launch (clip, the four double-double sums and their means, the packed panel) and
+// the replicate launch over `items` replicates of the nseg >= 1 segments in `tab` (device).  c: any
+// segment's constants (n, normalise, L, nd are call-wide).  Item i of segment s is replicate
+// s.rep_begin + (i - s.first), record out[s.out_row + (i - s.first)].
+int launch_sign_panel(const SignConst& c, const double* X, const double* Y, double* means, void* xyc,
+                      const SignSegConst* tab, int nseg, int64_t items, dcor_rep_out* out,
+                      void* stream);
+
 // The auxiliary streams and events a premat sub-G launch may use; default: none.
 struct PrematAux {
   // if non-null the epilogue runs on epi_stream after epi_event, recorded on `stream` behind the

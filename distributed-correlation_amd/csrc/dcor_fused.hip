@@ -194,57 +194,8 @@ __device__ __forceinline__ void sample_lap(const DgpConst& g, uint32_t i, uint32
   }
 }
 
-__device__ __forceinline__ uint32_t word(const U4& w, uint32_t q) {
-  return q == 0 ? w.w0 : (q == 1 ? w.w1 : (q == 2 ? w.w2 : w.w3));
-}
-
-struct FlipGen {  // sign-family INT flips, 4 per Philox block (SITE_FLIP), cached per block
-  uint32_t cidx;
-  U4 cw;
-  __device__ __forceinline__ int get(uint32_t i, uint32_t rep, uint32_t k0, uint32_t k1,
-                                     uint64_t p) {
-    const uint32_t bi = i >> 2;
-    if (bi != cidx) { cw = draw(bi, rep, DCOR_SITE_FLIP, k0, k1); cidx = bi; }
-    return ((uint64_t)word(cw, i & 3) < p) ? 1 : -1;  // 2*S - 1 (vert-cor.R:175-179)
-  }
-};
-
-// mixquant inside the workgroup: keys = z + c*l from Philox, then the order statistic.
-__device__ __forceinline__ double mixquant_fused(const MixConst& mx, double c, uint32_t rep,
-                                                 uint32_t k0, uint32_t k1, SelScratch* sc) {
-  if (threadIdx.x == 0) sc->nan_cnt = 0;
-  __syncthreads();
-  double val[SEL_VPT];
-  int nn = 0;
-#pragma unroll
-  for (int s = 0; s < SEL_VPT / 2; ++s) {
-    const int b = threadIdx.x + s * DCOR_BLOCK;  // Philox block b -> elements 2b, 2b+1
-    val[2 * s] = val[2 * s + 1] = dnan();
-    if (2 * b < mx.nsim) {
-      const U4 wz = draw((uint32_t)b, rep, DCOR_SITE_MIX_Z, k0, k1);
-      const U4 wl = draw((uint32_t)b, rep, DCOR_SITE_MIX_L, k0, k1);
-      double z0, z1;
-      normal_pair(wz, &z0, &z1);
-      val[2 * s] = z0 + c * unit_laplace(u53(wl.w0, wl.w1));
-      nn += (val[2 * s] != val[2 * s]);
-      if (2 * b + 1 < mx.nsim) {
-        val[2 * s + 1] = z1 + c * unit_laplace(u53(wl.w2, wl.w3));
-        nn += (val[2 * s + 1] != val[2 * s + 1]);
-      }
-    }
-  }
-  if (nn) atomicAdd(&sc->nan_cnt, nn);
-  __syncthreads();
-  return value_select(val, mx.pos, mx.nsim - sc->nan_cnt, sc);
-}
-
-__device__ __forceinline__ void scalar_laplace(uint32_t rep, uint32_t k0, uint32_t k1, double* lap) {
-  if (threadIdx.x < 5) {  // SITE_SCALAR blocks 0..4: NI mu/m2 X, NI mu/m2 Y, INT ..., Z
-    const U4 w = draw((uint32_t)threadIdx.x, rep, DCOR_SITE_SCALAR, k0, k1);
-    lap[2 * threadIdx.x] = unit_laplace(u53(w.w0, w.w1));
-    lap[2 * threadIdx.x + 1] = unit_laplace(u53(w.w2, w.w3));
-  }
-}
+// word, FlipGen, mixquant_fused, scalar_laplace, sign_finish: dcor_common.h (shared with the
+// sign-family panel kernel of dcor_signpanel.hip).
 
 // Wave-level mixquant from Philox (one replicate per wave): the same elements as
 // mixquant_fused, VPL keys per lane, written to the wave's LDS and selected there.
@@ -275,27 +226,6 @@ __device__ __forceinline__ double wave_mixquant_fused(const MixConst& mx, double
   }
   wave_sync();
   return wave_select_lds<VPL>(ws->keys, mx.pos, &ws->sel);
-}
-
-// INT epilogue + CI write shared by the sign kernels (vert-cor.R:281-313).
-__device__ __forceinline__ void sign_finish(const SignConst& c, uint32_t rep, DD sT, DD sT2,
-                                            long long core, bool any_ni, bool any_int,
-                                            const double* lap, SelScratch* sel,
-                                            dcor_rep_out* dst) {
-  double o[6];
-  ni_sign_result(c, sT, sT2, any_ni, o);
-  double rho, eta, se, cstar;
-  int_sign_point(c, core, lap[8], rho, eta, se, cstar);
-  double w;
-  if (c.mode_normal)
-    w = mixquant_fused(c.mix, cstar, rep, c.k0, c.k1, sel) * se;
-  else
-    w = c.w_laplace;
-  o[3] = rho;
-  o[4] = sin(M_PI / 2.0 * rmax(eta - w, -1.0));
-  o[5] = sin(M_PI / 2.0 * rmin(eta + w, 1.0));
-  if (any_int) o[3] = o[4] = o[5] = dnan();
-  if (threadIdx.x == 0) *dst = dcor_rep_out{o[0], o[1], o[2], o[3], o[4], o[5]};
 }
 
 // ======================================== fused sign family, one pass (hot) ===

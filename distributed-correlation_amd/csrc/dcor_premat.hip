@@ -2039,8 +2039,8 @@ static inline int last_err() { return (int)hipGetLastError(); }
 // workgroups per CU at `threads` and `lds` dynamic LDS bytes), at most one per item.  lds_limit
 // != 0 first raises the kernel's dynamic-LDS limit to it -- per call: the attribute is per device,
 // and one process may drive several GPUs (nothing here is cached across calls either).
-static int persistent_grid(const void* kernel, int threads, size_t lds, int64_t items, int64_t* grid,
-                           int lds_limit = 0) {
+int persistent_grid(const void* kernel, int threads, size_t lds, int64_t items, int64_t* grid,
+                    int lds_limit) {
   if (lds_limit != 0 &&
       hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit) != hipSuccess)
     return last_err();

@@ -95,6 +95,18 @@ class HrsSegment(C.Structure):
                 ("rep_begin", C.c_int64), ("reps", C.c_int64), ("out_row", C.c_int64)]
 
 
+class SignPanelDesc(C.Structure):
+    """dcor_sign_panel_desc (include/dcor.h): the shared panel and the call-wide settings."""
+    _fields_ = [("n", C.c_int64), ("X", _P), ("Y", _P), ("alpha", C.c_double),
+                ("normalise", C.c_int32), ("ci_mode", C.c_int32), ("nsim", C.c_int64)]
+
+
+class SignSegment(C.Structure):
+    """dcor_sign_segment (include/dcor.h): one (eps pair, key, replicate range, output row)."""
+    _fields_ = [("eps1", C.c_double), ("eps2", C.c_double), ("seed", C.c_uint64),
+                ("rep_begin", C.c_int64), ("reps", C.c_int64), ("out_row", C.c_int64)]
+
+
 _D = C.POINTER(C.c_double)
 _I64 = C.POINTER(C.c_int64)
 
@@ -154,6 +166,8 @@ SIGNATURES = {
                                         _P, _P]),
     "dcor_hrs_fused_sweep_launch": (C.c_int, [C.POINTER(PrematSubg), _P, C.POINTER(HrsSegment), C.c_int64,
                                               _P, _P]),
+    "dcor_sign_panel_launch": (C.c_int, [C.POINTER(SignPanelDesc), C.POINTER(SignSegment), C.c_int64,
+                                         _P, _P]),
     "dcor_batch_geometry": (C.c_int, [C.c_int64, C.c_double, C.c_double, C.c_int, C.c_int, _I64]),
     "dcor_ci_ni_signbatch": (C.c_int, [_D, _D, C.c_int64, C.c_double, C.c_double, C.c_double,
                                        C.c_int, _D, _D, _D, _D]),

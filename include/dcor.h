@@ -374,6 +374,54 @@ int dcor_hrs_fused_sweep_launch(const dcor_premat_subg* base, const dcor_panel* 
                                 const dcor_hrs_segment* segs, int64_t nseg, dcor_rep_out* d_out,
                                 void* stream);
 
+/* Sign-family replicates (ci_NI_signbatch + ci_INT_signflip, vert-cor.R:204-317) on the caller's
+ * own (X, Y), prepared once and shared by every replicate, with every noise draw made inside the
+ * kernel: the sign family's counterpart of dcor_hrs_fused_sweep_launch, and of running
+ * ver-cor-subG.R:179-195 with use_subG = FALSE on one data set.  Replicate rep_begin + j of a
+ * segment goes to d_out[out_row + j].  One preparation launch (the clip at sqrt(2 log n), the four
+ * double-double sums of priv_standardize and their means, the panel packed as (xc, yc) pairs; one
+ * workgroup, a fixed order) and one replicate launch cover every segment, whatever its (eps1,
+ * eps2): the batch geometry (m, k), the flip probability and the CI mode are per segment.
+ *
+ * Draw contract: the fused engine's (the DCOR_SITE_* list below) with the DGP samples replaced by
+ * the panel.  Philox key = the segment's seed, counter = (index, replicate, site, 0):
+ *   DCOR_SITE_SCALAR  blocks 0..3: the (mu, m2) unit Laplace pairs of the NI-X, NI-Y, INT-X, INT-Y
+ *                     standardisations; block 4, words 0,1: Z (vert-cor.R:188);
+ *   DCOR_SITE_NI_LAP  block j: batch j's unit Laplace for X (w0, w1) and Y (w2, w3);
+ *   DCOR_SITE_FLIP    sample i: block i >> 2, word i & 3, S_i = (word < ceil(p 2^32));
+ *   DCOR_SITE_MIX_Z, DCOR_SITE_MIX_L: mixquant's normals and unit Laplace, 2 per block.
+ * So a panel replicate uses the draws of the same replicate of dcor_sim_launch on a sign-family
+ * cell with that seed whose DGP takes its flips from DCOR_SITE_FLIP (bounded factor, mixture): on
+ * that replicate's dcor_dgp_launch samples the two records agree to rounding.  Per-replicate
+ * results depend only on (panel, eps1, eps2, seed, replicate), never on the segment split or the
+ * order of segments, so any sharding over calls or GPUs by rep_begin is exact.
+ *
+ * NaN: with normalise = 0 a NaN among the first k m samples makes NI NaN, one anywhere makes INT
+ * NaN; with normalise = 1 a NaN anywhere reaches the means and makes both NaN (as
+ * dcor_premat_sign_launch and R).
+ * Checks, all before anything is enqueued and before any device access (an invalid call returns
+ * its code and leaves d_out untouched): non-null p, X, Y, segs, d_out; 1 <= n < 2^31; per segment
+ * eps1, eps2 > 0, reps, rep_begin, out_row >= 0, rep_begin + reps <= 2^32, k = floor(n / m) >= 1
+ * (else DCOR_EKLT1; the sign family's geometry of dcor_batch_geometry); alpha, ci_mode, nsim
+ * (<= 2048) as dcor_sim_launch; at most 2^31 - 1 replicates per call.  nseg == 0 or no replicates
+ * at all returns DCOR_OK with no device work.  Asynchronous on `stream`; scratch is stream-ordered
+ * (16 B per sample, the segment table); X, Y and segs are borrowed for the call only (X, Y until
+ * the call's work on `stream` has run). */
+typedef struct dcor_sign_panel_desc {
+  int64_t n;
+  const double *X, *Y;      /* DEVICE, [n], shared by every replicate; borrowed for the call */
+  double alpha;
+  int32_t normalise, ci_mode; /* as dcor_cell */
+  int64_t nsim;
+} dcor_sign_panel_desc;
+typedef struct dcor_sign_segment {
+  double eps1, eps2;
+  uint64_t seed;
+  int64_t rep_begin, reps, out_row;
+} dcor_sign_segment;
+int dcor_sign_panel_launch(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs,
+                           int64_t nseg, dcor_rep_out* d_out, void* stream);
+
 int dcor_premat_sign_launch(const dcor_premat_sign* d, dcor_rep_out* d_out, void* stream);
 int dcor_premat_subg_launch(const dcor_premat_subg* d, dcor_rep_out* d_out, void* stream);
 
