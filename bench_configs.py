@@ -456,6 +456,55 @@ def sign_panel(R, big=100_000):
                   "over every segment, records copied back")
 
 
+def sign_table(R, p=8, arm="both"):
+    """ST: the sign family on every column pair of a p-column stand-in table (n = 19,433): the
+    p (p - 1) / 2 pairs x 23 eps x R sweep in one dcor_sign_table_launch call (ST), and the same
+    work -- same table, eps grid, keys and R -- as one signpanel.sweep_segments call per pair
+    (ST-per-pair), the only route before the table entry.  arm: "table", "pairs" or "both".  Not in
+    the default list: reach it with --only ST (--only ST-table / ST-pairs for one arm)."""
+    import numpy as np
+    import torch
+    from dcor import hrs, signpanel
+    D = signpanel.standin_table(19433, p, 0.3)
+    pairs = signpanel.all_pairs(p)
+    ne = len(hrs.EPS_GRID)
+    seed = 1_000_000
+
+    def table():   # corr_matrix_sweep's segments and keys, without its host-side summaries
+        segs = [(a, b, e, e, seed + j * ne + idx, 0, R) for j, (a, b) in enumerate(pairs)
+                for idx, e in enumerate(hrs.EPS_GRID, start=1)]
+        return signpanel.table_segments(D, segs).reshape(len(pairs), ne, R, 6)
+
+    def per_pair():
+        cols = [np.ascontiguousarray(D[:, c]) for c in range(p)]
+        return np.stack([signpanel.sweep_segments(cols[a], cols[b], [(e, e, seed + j * ne + idx, 0, R)
+                                                                      for idx, e in enumerate(hrs.EPS_GRID, start=1)])
+                         for j, (a, b) in enumerate(pairs)]).reshape(len(pairs), ne, R, 6)
+
+    total = len(pairs) * ne * R
+    res = {}
+    for name, fn, kernel, note in (
+            ("ST", table, "k_sign_table_prep + k_sign_table",
+             "host wall time of one call: table upload, one preparation launch over the columns, one replicate "
+             "launch over every (pair, eps) segment, records copied back"),
+            ("ST-per-pair", per_pair, "k_sign_panel_prep + k_sign_panel",
+             "host wall time of one sweep_segments call per pair: two uploads, a preparation launch, a "
+             "replicate launch over the pair's 23 eps and a D2H wait each")):
+        if arm != "both" and (arm == "table") != (name == "ST"):
+            continue
+        fn()    # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res[name] = fn()
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        line(name, n=int(D.shape[0]), p=p, pairs=len(pairs), replicates=total, seconds=t, reps_per_s=total / t,
+             finite=bool(np.isfinite(res[name][..., [0, 3, 4, 5]]).all()), kernel=kernel, note=note)
+    if len(res) == 2:
+        same = bool(np.array_equal(res["ST"].view(np.uint64), res["ST-per-pair"].view(np.uint64)))
+        print(json.dumps({"config": "ST-check", "records_bit_equal": same}), flush=True)
+
+
 def subg():
     from dcor.sim import CellSpec, simulate
     cell = CellSpec(n=100_000, rho=0.5, eps1=1.0, eps2=1.0, family="subG", dgp="bounded_factor", seed=5)
@@ -760,6 +809,9 @@ def main():
     if "HS" in which: hrs_sweep(a.hs_R)
     if "HSf" in which: hrs_sweep_fused(a.hs_R)
     if "SP" in which: sign_panel(a.hs_R)
+    if "ST" in which: sign_table(a.hs_R)
+    if "ST-table" in which: sign_table(a.hs_R, arm="table")
+    if "ST-pairs" in which: sign_table(a.hs_R, arm="pairs")
     if "S" in which: subg()
     if "R1" in which: rstream_c1()
     if "RG" in which: rstream_grid()

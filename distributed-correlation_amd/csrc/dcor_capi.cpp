@@ -1511,6 +1511,84 @@ int dcor_sign_panel_launch(const dcor_sign_panel_desc* p, const dcor_sign_segmen
   return DCOR_OK;
 }
 
+namespace {
+// The host half of dcor_sign_table_launch: every check of the call, then the device table of the
+// segments with reps > 0 in call order.  Touches no device.
+int plan_sign_table(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs, int64_t nseg,
+                    std::vector<SignPairSegConst>& tab, int64_t* items_out) {
+  if (t->p < 1 || t->p > 0x7fffffffLL)
+    return fail(DCOR_EINVAL, "sign_table: p must be in [1, 2^31) (got %lld)", (long long)t->p);
+  if (t->ld < t->n)
+    return fail(DCOR_EINVAL, "sign_table: ld = %lld < n = %lld", (long long)t->ld, (long long)t->n);
+  int64_t items = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_sign_pair_segment& g = segs[i];
+    if (g.reps < 0 || g.rep_begin < 0 || g.out_row < 0 || !(g.eps1 > 0.0) || !(g.eps2 > 0.0))
+      return fail(DCOR_EINVAL, "sign_table: segment %lld: need eps1, eps2 > 0, reps, rep_begin, out_row >= 0",
+                  (long long)i);
+    if (g.col_x < 0 || g.col_x >= t->p || g.col_y < 0 || g.col_y >= t->p)
+      return fail(DCOR_EINVAL, "sign_table: segment %lld: columns (%d, %d) outside [0, %lld)", (long long)i,
+                  (int)g.col_x, (int)g.col_y, (long long)t->p);
+    if (rep_range_exceeds(g.rep_begin, g.reps))
+      return fail(DCOR_EINVAL, "sign_table: segment %lld: replicate range exceeds 2^32", (long long)i);
+    items += g.reps;   // reps <= 2^32 each: no overflow below 2^31 segments
+    if (items > 0x7fffffffLL)
+      return fail(DCOR_EINVAL, "sign_table: more than 2^31 - 1 replicates in one call");
+  }
+  int64_t first = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_sign_pair_segment& g = segs[i];
+    SignPairSegConst s;
+    std::memset(&s, 0, sizeof(s));
+    if (int st = make_sign(t->n, g.eps1, g.eps2, t->alpha, t->normalise, t->ci_mode, t->nsim, false, s.s))
+      return st;
+    if (g.reps == 0) continue;
+    s.s.k0 = (uint32_t)g.seed; s.s.k1 = (uint32_t)(g.seed >> 32);
+    s.s.rep_begin = g.rep_begin;
+    s.first = first; s.out_row = g.out_row;
+    s.col_x = g.col_x; s.col_y = g.col_y;
+    first += g.reps;
+    tab.push_back(s);
+  }
+  // after make_sign: n is in [1, 2^31) here
+  if (!SignTableLayout((int64_t)tab.size(), t->n, t->p).ok)
+    return fail(DCOR_EINVAL, "sign_table: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)",
+                (long long)t->p, (long long)t->n);
+  *items_out = items;
+  return DCOR_OK;
+}
+}  // namespace
+
+int dcor_sign_table_launch(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs,
+                           int64_t nseg, dcor_rep_out* d_out, void* stream) {
+  if (!t || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
+    return fail(DCOR_EINVAL, "sign_table: null argument");
+  if (nseg == 0) return DCOR_OK;   // nothing to run
+  if (!t->D) return fail(DCOR_EINVAL, "sign_table: null argument (D)");
+  std::vector<SignPairSegConst> tab;
+  int64_t items = 0;
+  if (int st = plan_sign_table(t, segs, nseg, tab, &items)) return st;
+  if (items == 0) return DCOR_OK;
+  if (int st = need_device()) return st;
+  const SignTableLayout lay((int64_t)tab.size(), t->n, t->p);
+  void* buf = nullptr;
+  const hipStream_t st = (hipStream_t)stream;
+  if (hipMallocAsync(&buf, lay.bytes, st) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(DCOR_ENOMEM, "sign_table: cannot allocate %zu scratch bytes", lay.bytes);
+  }
+  count_alloc();
+  // from pageable memory: the copy has left `tab` when the call returns
+  int rc = (int)hipMemcpyAsync(lay.tab(buf), tab.data(), tab.size() * sizeof(SignPairSegConst),
+                               hipMemcpyHostToDevice, st);
+  if (!rc)
+    rc = launch_sign_table(tab[0].s, t->D, t->p, t->ld, lay.means(buf), lay.cols(buf), lay.tab(buf),
+                           (int)tab.size(), items, d_out, stream);
+  (void)hipFreeAsync(buf, st);
+  if (rc) return hip_fail((hipError_t)rc, "sign_table launch");
+  return DCOR_OK;
+}
+
 int dcor_panel_dict_probe(const double* d_X, const double* d_Y, int64_t n, int* ok) {
   if (!d_X || !d_Y || !ok || n < 1) return fail(DCOR_EINVAL, "panel_dict_probe: bad arguments");
   if (int st = need_device()) return st;

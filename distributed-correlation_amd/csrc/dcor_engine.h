@@ -381,6 +381,42 @@ int launch_sign_panel(const SignConst& c, const double* X, const double* Y, doub
                       const SignSegConst* tab, int nseg, int64_t items, dcor_rep_out* out,
                       void* stream);
 
+// ---- sign family on the column pairs of a shared table (dcor_sign_table_launch) ----
+// A sign-panel segment and the two columns it reads: X = column col_x, Y = column col_y.
+struct SignPairSegConst : SignSegConst {
+  int32_t col_x, col_y;
+};
+// Sign-table scratch: the per-column means (mean(xc), mean(xc^2) of column c at means[2 c],
+// means[2 c + 1]) | the segment table | the p clipped columns as plain doubles, each zero-padded
+// to npad = n rounded up to a whole 4-sample flip block, so every column starts 32-B aligned.
+// Every region starts 256-B aligned when the base is.  ok is false when p * npad * 8 bytes (or the
+// total) is not representable.
+struct SignTableLayout {
+  int64_t npad;
+  size_t tab_off = 0, cols_off = 0, bytes = 0;
+  bool ok = false;
+  SignTableLayout(int64_t nseg, int64_t n, int64_t p) : npad((n + 3) & ~(int64_t)3) {
+    const size_t lim = SIZE_MAX / 2;
+    if (n < 1 || p < 1 || nseg < 0 || (size_t)p > lim / 16 || (size_t)nseg > lim / sizeof(SignPairSegConst))
+      return;
+    tab_off = al256((size_t)p * 2 * sizeof(double));
+    cols_off = tab_off + al256((size_t)nseg * sizeof(SignPairSegConst));
+    const size_t col_bytes = (size_t)npad * sizeof(double);
+    if ((size_t)p > (lim - cols_off) / col_bytes) return;
+    bytes = cols_off + (size_t)p * col_bytes;
+    ok = true;
+  }
+  double* means(void* base) const { return (double*)base; }
+  SignPairSegConst* tab(void* base) const { return (SignPairSegConst*)((char*)base + tab_off); }
+  double* cols(void* base) const { return (double*)((char*)base + cols_off); }
+};
+// The preparation launch (one workgroup per column of D: clip, the two double-double sums and
+// their means in k_sign_panel_prep's order, the column stored at pitch npad) and the replicate
+// launch over `items` replicates of the nseg >= 1 segments in `tab` (device), as launch_sign_panel.
+int launch_sign_table(const SignConst& c, const double* D, int64_t p, int64_t ld, double* means,
+                      double* cols, const SignPairSegConst* tab, int nseg, int64_t items,
+                      dcor_rep_out* out, void* stream);
+
 // The auxiliary streams and events a premat sub-G launch may use; default: none.
 struct PrematAux {
   // if non-null the epilogue runs on epi_stream after epi_event, recorded on `stream` behind the

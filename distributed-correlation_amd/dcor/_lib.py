@@ -107,6 +107,18 @@ class SignSegment(C.Structure):
                 ("rep_begin", C.c_int64), ("reps", C.c_int64), ("out_row", C.c_int64)]
 
 
+class SignTableDesc(C.Structure):
+    """dcor_sign_table_desc (include/dcor.h): the shared table (p columns of n samples, ld apart)
+    and the call-wide settings."""
+    _fields_ = [("n", C.c_int64), ("p", C.c_int64), ("ld", C.c_int64), ("D", _P), ("alpha", C.c_double),
+                ("normalise", C.c_int32), ("ci_mode", C.c_int32), ("nsim", C.c_int64)]
+
+
+class SignPairSegment(C.Structure):
+    """dcor_sign_pair_segment (include/dcor.h): a dcor_sign_segment and its (X, Y) columns."""
+    _fields_ = SignSegment._fields_ + [("col_x", C.c_int32), ("col_y", C.c_int32)]
+
+
 _D = C.POINTER(C.c_double)
 _I64 = C.POINTER(C.c_int64)
 
@@ -167,6 +179,8 @@ SIGNATURES = {
     "dcor_hrs_fused_sweep_launch": (C.c_int, [C.POINTER(PrematSubg), _P, C.POINTER(HrsSegment), C.c_int64,
                                               _P, _P]),
     "dcor_sign_panel_launch": (C.c_int, [C.POINTER(SignPanelDesc), C.POINTER(SignSegment), C.c_int64,
+                                         _P, _P]),
+    "dcor_sign_table_launch": (C.c_int, [C.POINTER(SignTableDesc), C.POINTER(SignPairSegment), C.c_int64,
                                          _P, _P]),
     "dcor_batch_geometry": (C.c_int, [C.c_int64, C.c_double, C.c_double, C.c_int, C.c_int, _I64]),
     "dcor_ci_ni_signbatch": (C.c_int, [_D, _D, C.c_int64, C.c_double, C.c_double, C.c_double,

@@ -205,3 +205,42 @@ def eps_sweep_distributed(age_z, bmi_z, lam_age, lam_bmi, eps_grid=None, reps=No
     counts = [shard(len(eps_grid) * reps, r, world)[1] for r in range(world)]
     runs = gather_rows(local, counts, group).reshape(len(eps_grid), reps, 6)
     return hrs.sweep_summaries(eps_grid, runs)
+
+
+# ------------------------------------------------- sign family on a shared table's column pairs
+def segment_shard(seg_reps, rank: int, world: int):
+    """Rank `rank`'s part of a call's flattened (segment, replicate) space, segment j holding
+    seg_reps[j] replicates: the contiguous range shard(sum(seg_reps), rank, world) as (segment index,
+    first replicate offset, count) pieces -- sweep_shard for segments of unequal length."""
+    starts = np.concatenate([[0], np.cumsum([int(c) for c in seg_reps])])
+    b0, nb = shard(int(starts[-1]), rank, world)
+    out, i = [], b0
+    j = int(np.searchsorted(starts, b0, side="right")) - 1
+    while i < b0 + nb:
+        while starts[j + 1] <= i:   # segments without replicates
+            j += 1
+        c = int(min(starts[j + 1], b0 + nb) - i)
+        out.append((j, int(i - starts[j]), c))
+        i += c
+    return out
+
+
+def sign_table_distributed(D, segs, group=None, **kw):
+    """dcor.signpanel.table_segments over G ranks: the flattened (segment, replicate) space of segs
+    [(col_x, col_y, eps1, eps2, seed, rep_begin, reps), ...] is split into contiguous per-rank
+    ranges (segment_shard), each rank runs its pieces -- the segment's pair, eps and key, rep_begin
+    moved on by the piece's offset -- in one native call, and the records are all-gathered in rank
+    order.  A record depends only on (columns, eps1, eps2, seed, replicate), so the [sum(reps), 6]
+    result, identical on all ranks, equals one process's table_segments(D, segs) byte for byte."""
+    import torch.distributed as dist
+
+    from . import signpanel
+    segs = list(segs)
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    seg_reps = [int(s[6]) for s in segs]
+    if sum(seg_reps) == 0:   # the same on every rank: nothing to run or gather
+        return np.zeros((0, 6))
+    mine = [(*segs[j][:5], int(segs[j][5]) + r0, c) for j, r0, c in segment_shard(seg_reps, rank, world)]
+    local = signpanel.table_segments(D, mine, **kw) if mine else np.zeros((0, 6))
+    counts = [shard(sum(seg_reps), r, world)[1] for r in range(world)]
+    return gather_rows(local, counts, group)

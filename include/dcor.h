@@ -422,6 +422,42 @@ typedef struct dcor_sign_segment {
 int dcor_sign_panel_launch(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream);
 
+/* The same replicates for any column pairs of one shared table (vertically partitioned data:
+ * several variables on either server, the private correlation of every pair).  D holds p columns
+ * of n samples, column c at D + c * ld.  A segment names its pair: X = column col_x (the sender
+ * side of the panel entry's X), Y = column col_y; (a, b) and (b, a) are different segments and
+ * col_x == col_y is allowed.  The records of a segment equal, byte for byte, the records of
+ * dcor_sign_panel_launch on X = column col_x, Y = column col_y with the same (eps1, eps2, seed,
+ * rep_begin, reps): the same per-replicate code, the draw contract above, the same NaN rules (a
+ * NaN in a column reaches only the pairs that name it).  One preparation launch (one workgroup
+ * per column, the panel entry's clip and summation order, so a column's two means are the bits
+ * the panel entry forms for it on either side) and one replicate launch cover every pair and
+ * every (eps1, eps2).
+ * Checks, all before anything is enqueued and before any device access: those of
+ * dcor_sign_panel_launch (non-null t, D, segs, d_out; n; per segment eps, reps, rep_begin,
+ * out_row, the replicate range, k >= 1 else DCOR_EKLT1; alpha, ci_mode, nsim; at most 2^31 - 1
+ * replicates per call), and 1 <= p < 2^31, ld >= n, 0 <= col_x, col_y < p (dcor_last_error names
+ * the segment), p * npad * 8 scratch bytes representable (npad: n rounded up to a multiple of 4).
+ * nseg == 0 or no replicates at all returns DCOR_OK with no device work.  Asynchronous on
+ * `stream`; scratch is stream-ordered (8 B per sample and column, 16 B per column, the segment
+ * table); D and segs are borrowed for the call only (D until the call's work on `stream` has
+ * run). */
+typedef struct dcor_sign_table_desc {
+  int64_t n, p, ld;         /* samples per column, columns, elements between column starts */
+  const double* D;          /* DEVICE, column c = D + c * ld; borrowed for the call */
+  double alpha;
+  int32_t normalise, ci_mode; /* as dcor_cell */
+  int64_t nsim;
+} dcor_sign_table_desc;
+typedef struct dcor_sign_pair_segment {
+  double eps1, eps2;
+  uint64_t seed;
+  int64_t rep_begin, reps, out_row;
+  int32_t col_x, col_y;
+} dcor_sign_pair_segment;
+int dcor_sign_table_launch(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs,
+                           int64_t nseg, dcor_rep_out* d_out, void* stream);
+
 int dcor_premat_sign_launch(const dcor_premat_sign* d, dcor_rep_out* d_out, void* stream);
 int dcor_premat_subg_launch(const dcor_premat_subg* d, dcor_rep_out* d_out, void* stream);
 
