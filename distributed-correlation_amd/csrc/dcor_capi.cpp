@@ -1754,6 +1754,24 @@ int dcor_mixquant(const double* z, const double* l, int64_t nsim, double c, doub
   return DCOR_OK;
 }
 
+int dcor_diag_select(const double* h_keys, int64_t nkeys, int64_t nsets, int32_t pos, int which,
+                     double* h_out) {
+  if (!h_keys || !h_out) return fail(DCOR_EINVAL, "null argument");
+  if (which < 0 || which > 5) return fail(DCOR_EINVAL, "which must be in [0, 5]");
+  const int64_t kmax = (which == 2 || which == 4) ? 1024 : 2048;
+  if (nkeys < 1 || nkeys > kmax) return fail(DCOR_EINVAL, "nkeys must be in [1, %lld] for which = %d", (long long)kmax, which);
+  if (nsets < 0 || nsets > (int64_t)1 << 20) return fail(DCOR_EINVAL, "nsets must be in [0, 2^20]");
+  if (nsets == 0) return DCOR_OK;
+  if (int st = need_device()) return st;
+  DevBuf bk, bo;
+  if (int st = upload(bk, h_keys, (size_t)(nkeys * nsets))) return st;
+  HIPCHK(bo.alloc(sizeof(double) * (size_t)nsets));
+  const int rc = launch_diag_select(bk.as<double>(), (int32_t)nkeys, nsets, pos, which, bo.as<double>(), nullptr);
+  if (rc) return hip_fail((hipError_t)rc, "diag_select launch");
+  HIPCHK(hipMemcpy(h_out, bo.p, sizeof(double) * (size_t)nsets, hipMemcpyDeviceToHost));
+  return DCOR_OK;
+}
+
 int dcor_priv_standardize(const double* v, int64_t n, double eps_norm, double L_raw,
                           const double lap[2], double* out) {
   if (!v || !lap || !out || n < 1) return fail(DCOR_EINVAL, "bad argument");

@@ -651,8 +651,18 @@ __device__ __forceinline__ double value_select(const double (&v)[SEL_VPT], int p
 // waves of a workgroup finish four replicates independently.  Same value-binning scheme as
 // value_select: a min/max reduction, a 256-bin LDS histogram of the active keys, the bin
 // holding rank k is either ranked directly (<= 64 keys) or becomes the new active set
-// (iterate; each round removes at least one distinct value).  Infinite keys are peeled off
-// first.  Lanes of one wave see each other's LDS writes after wave_sync (in-order LDS).
+// (iterate).  Infinite keys are peeled off first.  Lanes of one wave see each other's LDS writes
+// after wave_sync (in-order LDS).
+// Rounds: a by-value round only promises to drop one distinct value (the minimum and the maximum
+// never share a bin), so a crowded low value under a ladder of values 2^8 apart would take a round
+// per rung.  After WSEL_VALUE_ROUNDS rounds the binning therefore goes by the integer key, whatever
+// the range: bin = (key - klo) >> sh keeps the top 8 bits of d = khi - klo, the chosen bin spans
+// less than 2^sh, so d loses 8 bits a round -- 64, 56, ..., 8 bits -- and the round after d < 2^8
+// sees one distinct key: WSEL_KEY_ROUNDS = 9 by-key rounds at the most.  The draws the engine
+// generates finish in one or two rounds; the switch count leaves them two more.
+#define WSEL_VALUE_ROUNDS 4
+#define WSEL_KEY_ROUNDS 9
+#define WSEL_ROUNDS (WSEL_VALUE_ROUNDS + WSEL_KEY_ROUNDS)
 struct WaveSel {
   uint32_t hist[256];
   double cand[64];
@@ -719,7 +729,7 @@ __device__ __forceinline__ double wave_select(const double (&v)[VPL], int pos, W
     act &= ~(mlo | mhi);
     k -= nlo;
   }
-  for (int iter = 0; iter < 80; ++iter) {
+  for (int iter = 0; iter < WSEL_ROUNDS; ++iter) {
     double lo = INF, hi = -INF;
 #pragma unroll
     for (int s = 0; s < VPL; ++s)
@@ -731,7 +741,7 @@ __device__ __forceinline__ double wave_select(const double (&v)[VPL], int pos, W
     bm.lo = lo;
     const double h = 0.5 * hi - 0.5 * lo;
     bm.scale = 128.0 / h;
-    bm.by_value = (h > 0.0) && (bm.scale < INF);
+    bm.by_value = (h > 0.0) && (bm.scale < INF) && iter < WSEL_VALUE_ROUNDS;
     bm.klo = sel_key(lo);
     {
       const unsigned long long d = sel_key(hi) - bm.klo;
@@ -853,7 +863,7 @@ __device__ __forceinline__ double wave_select_lds(const double* kv, int pos, Wav
     act &= ~(mlo | mhi);
     k -= nlo;
   }
-  for (int iter = 0; iter < 80; ++iter) {
+  for (int iter = 0; iter < WSEL_ROUNDS; ++iter) {
     double lo = INF, hi = -INF;
 #pragma unroll
     for (int s = 0; s < VPL; ++s)
@@ -863,7 +873,7 @@ __device__ __forceinline__ double wave_select_lds(const double* kv, int pos, Wav
     if (!(hi > lo)) return lo;  // every active key equal
     const double h = 0.5 * hi - 0.5 * lo;
     const double scale = 128.0 / h;
-    const bool by_value = (h > 0.0) && (scale < INF);
+    const bool by_value = (h > 0.0) && (scale < INF) && iter < WSEL_VALUE_ROUNDS;
     const unsigned long long klo = sel_key(lo);
     int sh;
     {

@@ -435,6 +435,9 @@ int launch_accumulate(const dcor_rep_out* d_out, int64_t count, double rho, dcor
                       void* stream);
 int launch_mixquant(const double* z, const double* l, int32_t nsim, double c, int32_t pos,
                     double* out, void* stream);
+// dcor_diag_select: selector `which` on keys[nsets][nkeys] (device), out[nsets].
+int launch_diag_select(const double* keys, int32_t nkeys, int64_t nsets, int32_t pos, int which,
+                       double* out, void* stream);
 int launch_priv_standardize(const double* v, int64_t n, double L, double s_mu, double s_m2,
                             const double* lap2, double* out, void* stream);
 int launch_draws(int kind, uint32_t k0, uint32_t k1, uint32_t site, int64_t rep_begin,

@@ -5,6 +5,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "dcor_common.h"
 
@@ -1268,6 +1269,78 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_mixquant(const double* z, const 
   if (threadIdx.x == 0) *out = q;
 }
 
+// dcor_diag_select: the selectors of dcor_device.h on caller keys (NaN = absent), so tests reach
+// them with key sets the generated draws never form.  Workgroup selectors: one workgroup per set,
+// key i at thread i % DCOR_BLOCK, slot i / DCOR_BLOCK, `valid` counted as mixquant_loaded counts it.
+template <bool RADIX>
+__global__ __launch_bounds__(DCOR_BLOCK) void k_diag_select_wg(const double* __restrict__ keys, int32_t nkeys,
+                                                               int32_t pos, double* out) {
+  __shared__ SelScratch sel;
+  const double* kv = keys + (int64_t)blockIdx.x * nkeys;
+  if (threadIdx.x == 0) sel.nan_cnt = 0;
+  __syncthreads();
+  double val[SEL_VPT];
+  int nn = 0;
+#pragma unroll
+  for (int s = 0; s < SEL_VPT; ++s) {
+    const int i = threadIdx.x + s * DCOR_BLOCK;
+    val[s] = dnan();
+    if (i < nkeys) {
+      val[s] = kv[i];
+      nn += (val[s] != val[s]);
+    }
+  }
+  if (nn) atomicAdd(&sel.nan_cnt, nn);
+  __syncthreads();
+  const int valid = nkeys - sel.nan_cnt;
+  double q;
+  if constexpr (RADIX) {
+    unsigned long long key[SEL_VPT];
+#pragma unroll
+    for (int s = 0; s < SEL_VPT; ++s) key[s] = sel_key(val[s]);
+    q = reg_select(key, pos, valid, &sel);
+  } else {
+    q = value_select(val, pos, valid, &sel);
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = q;
+}
+
+// Wave selectors: one wave per set, DCOR_WAVES sets per workgroup, key i at lane i % 64, slot i / 64
+// (the epilogues' layout), in registers (wave_select) or in the wave's LDS (wave_select_lds).
+template <int VPL>
+struct DiagWaveKeys {
+  double keys[64 * VPL];
+  WaveSelL sel;
+};
+template <int VPL, bool LDS>
+__global__ __launch_bounds__(DCOR_BLOCK) void k_diag_select_wave(const double* __restrict__ keys, int32_t nkeys,
+                                                                 int64_t nsets, int32_t pos, double* out) {
+  __shared__ typename std::conditional<LDS, DiagWaveKeys<VPL>, WaveSel>::type wsel[DCOR_WAVES];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t set = (int64_t)blockIdx.x * DCOR_WAVES + wv;
+  if (set >= nsets) return;  // whole waves only
+  const double* kv = keys + set * nkeys;
+  double q;
+  if constexpr (LDS) {
+#pragma unroll
+    for (int s = 0; s < VPL; ++s) {
+      const int i = lane + 64 * s;
+      wsel[wv].keys[i] = i < nkeys ? kv[i] : dnan();
+    }
+    wave_sync();
+    q = wave_select_lds<VPL>(wsel[wv].keys, pos, &wsel[wv].sel);
+  } else {
+    double val[VPL];
+#pragma unroll
+    for (int s = 0; s < VPL; ++s) {
+      const int i = lane + 64 * s;
+      val[s] = i < nkeys ? kv[i] : dnan();
+    }
+    q = wave_select<VPL>(val, pos, &wsel[wv]);
+  }
+  if (lane == 0) out[set] = q;
+}
+
 // priv_standardize (vert-cor.R:322-348) over one vector (one workgroup).
 __global__ __launch_bounds__(DCOR_BLOCK) void k_priv_standardize(const double* v, int64_t n,
                                                                  double L, double s_mu,
@@ -2374,6 +2447,21 @@ int launch_mixquant(const double* z, const double* l, int32_t nsim, double c, in
   mx.pad = 0;
   hipLaunchKernelGGL(k_mixquant, dim3(1), dim3(DCOR_BLOCK), 0, (hipStream_t)stream, z, l, mx,
                      c, out);
+  return last_err();
+}
+int launch_diag_select(const double* keys, int32_t nkeys, int64_t nsets, int32_t pos, int which,
+                       double* out, void* stream) {
+  const dim3 wg((unsigned)nsets), wvs((unsigned)((nsets + DCOR_WAVES - 1) / DCOR_WAVES)), blk(DCOR_BLOCK);
+  hipStream_t st = (hipStream_t)stream;
+  switch (which) {
+    case 0: hipLaunchKernelGGL(k_diag_select_wg<false>, wg, blk, 0, st, keys, nkeys, pos, out); break;
+    case 1: hipLaunchKernelGGL(k_diag_select_wg<true>, wg, blk, 0, st, keys, nkeys, pos, out); break;
+    case 2: hipLaunchKernelGGL((k_diag_select_wave<16, false>), wvs, blk, 0, st, keys, nkeys, nsets, pos, out); break;
+    case 3: hipLaunchKernelGGL((k_diag_select_wave<32, false>), wvs, blk, 0, st, keys, nkeys, nsets, pos, out); break;
+    case 4: hipLaunchKernelGGL((k_diag_select_wave<16, true>), wvs, blk, 0, st, keys, nkeys, nsets, pos, out); break;
+    case 5: hipLaunchKernelGGL((k_diag_select_wave<32, true>), wvs, blk, 0, st, keys, nkeys, nsets, pos, out); break;
+    default: return (int)hipErrorInvalidValue;
+  }
   return last_err();
 }
 int launch_priv_standardize(const double* v, int64_t n, double L, double s_mu, double s_m2,

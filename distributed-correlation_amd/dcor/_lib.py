@@ -144,6 +144,7 @@ SIGNATURES = {
     "dcor_sim_chunking": (C.c_int, [C.POINTER(Cell), C.c_int64, _I64, _I64]),
     "dcor_diag_sign_pass": (C.c_int, [C.POINTER(Cell), C.c_int64, C.c_int64, C.c_int, _P]),
     "dcor_diag_sign_ties": (C.c_int, [C.POINTER(Cell), C.c_int64, C.c_int64, _I64]),
+    "dcor_diag_select": (C.c_int, [_D, C.c_int64, C.c_int64, C.c_int32, C.c_int, _D]),
     "dcor_lambda_n": (C.c_double, [C.c_double, C.c_double]),
     "dcor_lambda_int_n": (None, [C.c_double, C.c_double, C.c_double, C.c_double, _D]),
     "dcor_lambda_receiver_from_noise": (C.c_double, [C.c_double] * 4),

@@ -146,6 +146,15 @@ int dcor_diag_sign_pass(const dcor_cell* cell, int64_t rep_begin, int64_t reps, 
  * replicate, the number of NI batches whose record codes tied a private centre's code and took the
  * exact regeneration fix-up (the rare path of the one-pass sign kernels) into h_ties[reps]. */
 int dcor_diag_sign_ties(const dcor_cell* cell, int64_t rep_begin, int64_t reps, int64_t* h_ties);
+/* Test entry: one of the engine's order-statistic selectors on caller keys.  h_keys[nsets][nkeys]
+ * (host, NaN = absent), h_out[nsets] = sort(non-NaN keys of the set)[pos] (0-based; NaN when pos is
+ * outside [0, valid)).  which: 0 value_select, 1 reg_select (on the keys' integer map), one workgroup
+ * per set; 2 / 3 wave_select with 16 / 32 keys per lane, 4 / 5 wave_select_lds with 16 / 32, one wave
+ * per set and four sets per workgroup, key i at lane i % 64, slot i / 64.  1 <= nkeys <= 2048 (1024
+ * for which 2 and 4); 0 <= nsets <= 2^20, nsets = 0 returns DCOR_OK.  pos is not checked.
+ * Synchronous. */
+int dcor_diag_select(const double* h_keys, int64_t nkeys, int64_t nsets, int32_t pos, int which,
+                     double* h_out);
 
 /* ---- calibration scalars (host closed forms) ----------------------------- */
 /* lambda_n, ver-cor-subG.R:1 (= real-data-sims.R:109). */
