@@ -29,16 +29,6 @@ using namespace dcor;
 namespace dcor {
 namespace host {
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
 int hip_fail(hipError_t e, const char* what) {
   return fail(DCOR_EHIP, "%s: %s", what, hipGetErrorString(e));
 }
@@ -70,9 +60,6 @@ int need_device() {
   return DCOR_OK;
 }
 
-double r_min(double a, double b) { return (std::isnan(a) || std::isnan(b)) ? NAN : (a < b ? a : b); }
-double r_max(double a, double b) { return (std::isnan(a) || std::isnan(b)) ? NAN : (a > b ? a : b); }
-
 struct DevBuf {  // RAII device allocation for the host-pointer entry points
   void* p = nullptr;
   ~DevBuf() { if (p) (void)hipFree(p); }
@@ -92,24 +79,35 @@ int upload(DevBuf& b, const T* h, size_t count) {
   return DCOR_OK;
 }
 
-// T with (double)w * 2^-32 < p  <=>  w < T for every uint32 w: T = ceil(p * 2^32) clamped
-// to [0, 2^32] (p * 2^32 is exact).
-uint64_t u32_threshold(double p) {
-  if (!(p > 0)) return 0;
-  const double t = std::ceil(p * 4294967296.0);
-  return t >= 4294967296.0 ? (uint64_t)4294967296ull : (uint64_t)t;
+// One stream-ordered scratch block of `bytes` ("scratch" or "noise": `kind`) for the work
+// `run(buf)` enqueues on `stream`, whose status is returned; freed in stream order on every path
+// after a successful allocation.  Safe under concurrent launches on different streams.
+template <class Run>
+static int with_scratch(const char* entry, const char* kind, size_t bytes, void* stream, Run run) {
+  void* buf = nullptr;
+  const hipStream_t st = (hipStream_t)stream;
+  if (hipMallocAsync(&buf, bytes, st) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(DCOR_ENOMEM, "%s: cannot allocate %zu %s bytes", entry, bytes, kind);
+  }
+  count_alloc();
+  const int e = run(buf);
+  (void)hipFreeAsync(buf, st);
+  return e;
 }
 
-// MixConst for sort(x)[ceiling(p*nsim)], p = 1 - alpha/2.
-int make_mix(int64_t nsim, double alpha, MixConst& mx) {
-  if (nsim < 1 || nsim > 2048) return fail(DCOR_EINVAL, "nsim must be in [1, 2048] (got %lld)", (long long)nsim);
-  const double pos = std::ceil((1.0 - alpha / 2.0) * (double)nsim);
-  mx.nsim = (int32_t)nsim;
-  mx.pos = (pos >= 1 && pos <= (double)nsim) ? (int32_t)pos - 1 : -1;
-  mx.P = 1;
-  while (mx.P < mx.nsim) mx.P <<= 1;
-  mx.pad = 0;
-  return DCOR_OK;
+// with_scratch for a launch driven by a segment table: `tab` copied to buf + tab_off, then
+// `launch(buf)` (hipError_t as int).
+template <class T, class Launch>
+static int with_table(const char* entry, size_t bytes, const std::vector<T>& tab, size_t tab_off,
+                      void* stream, Launch launch) {
+  return with_scratch(entry, "scratch", bytes, stream, [&](void* buf) {
+    // from pageable memory: the copy has left `tab` when the call returns
+    int rc = (int)hipMemcpyAsync((char*)buf + tab_off, tab.data(), tab.size() * sizeof(T),
+                                 hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (!rc) rc = launch(buf);
+    return rc ? fail(DCOR_EHIP, "%s launch: %s", entry, hipGetErrorString((hipError_t)rc)) : DCOR_OK;
+  });
 }
 
 // MASS::mvrnorm factor A = V diag(sqrt(ev)) of the 2x2 covariance (vert-cor.R:389-394).
@@ -180,140 +178,6 @@ int make_dgp(const dcor_cell& c, DgpConst& g) {
   } else {
     return fail(DCOR_EINVAL, "unknown dgp %d", c.dgp);
   }
-  return DCOR_OK;
-}
-
-int check_common(int64_t n, double eps1, double eps2, double alpha) {
-  if (n < 1 || n > 0x7fffffffLL) return fail(DCOR_EINVAL, "n must be in [1, 2^31) (got %lld)", (long long)n);
-  if (!(eps1 > 0) || !(eps2 > 0) || !std::isfinite(eps1) || !std::isfinite(eps2))
-    return fail(DCOR_EINVAL, "eps1 > 0 and eps2 > 0 required (vert-cor.R:264)");
-  // The reference never checks alpha: qnorm(1 - alpha/2) and mixquant's
-  // sort(x)[ceiling((1 - alpha/2) nsim)] are evaluated as they come (alpha = 1: a zero-width
-  // CI; alpha < 0: NaN).  alpha >= 2 makes the mixquant index < 1, where R's x[0] is
-  // numeric(0) and run_sim_one's detail assignment fails, so it is refused here.
-  if (std::isnan(alpha) || !(alpha < 2))
-    return fail(DCOR_EINVAL, "alpha must be < 2 (R's mixquant index ceiling((1-alpha/2)*nsim) >= 1)");
-  return DCOR_OK;
-}
-
-// ci_NI_signbatch + ci_INT_signflip scalars (vert-cor.R:204-317).
-// allow_k0: INT-only single calls (ci_INT_signflip has no batch requirement).
-int make_sign(int64_t n, double eps1, double eps2, double alpha, int normalise, int mode,
-              int64_t nsim, bool allow_k0, SignConst& c) {
-  std::memset(&c, 0, sizeof(c));
-  if (int st = check_common(n, eps1, eps2, alpha)) return st;
-  const double nd = (double)n;
-  const double md = std::ceil(8.0 / (eps1 * eps2));                     // :207
-  const double kd = std::floor(nd / md);                                 // :208
-  if (!(kd >= 1) && !allow_k0)
-    return fail(DCOR_EKLT1, "ci_NI_signbatch: k = floor(n/m) = %g < 1 (n=%lld, m=%g; vert-cor.R:209)", kd, (long long)n, md);
-  if (md > 0x7fffffff) return fail(DCOR_EINVAL, "batch size m too large");
-  c.n = n; c.m = (int32_t)md; c.k = kd >= 1 ? (int64_t)kd : 0;
-  c.nd = nd; c.md = md; c.kd = kd;
-  c.pieces = sign_pieces(c.m);
-  {
-    int e = 0;
-    c.md_pow2 = (std::frexp(md, &e) == 0.5) ? 1 : 0;  // md = 2^(e-1): count / md == count * 2^(1-e)
-    c.inv_md = c.md_pow2 ? std::ldexp(1.0, 1 - e) : 0.0;
-  }
-  c.normalise = normalise ? 1 : 0;
-  const double L = std::sqrt(2.0 * std::log(nd));                        // :212
-  c.L = L;
-  c.s_mu_x = 2.0 * L / (nd * (eps1 / 2));                                // :335-336
-  c.s_m2_x = 2.0 * (L * L) / (nd * (eps1 / 2));                          // :339-340
-  c.s_mu_y = 2.0 * L / (nd * (eps2 / 2));
-  c.s_m2_y = 2.0 * (L * L) / (nd * (eps2 / 2));
-  c.bx = 2.0 / (md * eps1);                                              // :230
-  c.by = 2.0 / (md * eps2);                                              // :231
-  c.inv_k = 1.0 / kd;                                                    // :234
-  c.crit = dcor_qnorm(1.0 - alpha / 2.0);                                // :242
-  c.sqrt_k = std::sqrt(kd);
-  c.sender_is_X = (eps1 >= eps2) ? 1 : 0;                                // :275
-  const double eps_s = c.sender_is_X ? eps1 : eps2, eps_r = c.sender_is_X ? eps2 : eps1;
-  const double es = std::exp(eps_s);
-  c.pflip = es / (es + 1.0);                                             // :174
-  c.flipT = u32_threshold(c.pflip);
-  {
-    const double t = std::ceil(c.pflip * 16777216.0);  // exact scaling
-    c.flipT24 = t >= 16777216.0 ? 16777216u : (t > 0 ? (uint32_t)t : 0u);
-  }
-  c.scale_Z = 2.0 * (es + 1.0) / (nd * (es - 1.0) * eps_r);              // :186-187
-  c.coefZ = (es + 1.0) / (nd * (es - 1.0));                              // :190-191
-  const double q = (es - 1.0) / (es + 1.0);
-  c.q2 = q * q;                                                          // :284
-  c.ratio = (es + 1.0) / (es - 1.0);                                     // :289
-  c.inv_sqrt_n = 1.0 / std::sqrt(nd);
-  c.eps_r = eps_r;
-  c.w_laplace = (2.0 / (nd * eps_r)) * c.ratio * std::log(1.0 / alpha);  // :305-308
-  int md_ = mode;
-  if (md_ == DCOR_MODE_AUTO) md_ = (std::sqrt(nd) * eps_r > 0.5) ? DCOR_MODE_NORMAL : DCOR_MODE_LAPLACE;  // :294-296
-  else if (md_ != DCOR_MODE_NORMAL && md_ != DCOR_MODE_LAPLACE) return fail(DCOR_EINVAL, "ci_mode must be auto/normal/laplace");
-  c.mode_normal = (md_ == DCOR_MODE_NORMAL) ? 1 : 0;
-  if (int st = make_mix(nsim, alpha, c.mix)) return st;
-  return DCOR_OK;
-}
-
-// correlation_NI_subG + ci_INT_subG scalars (ver-cor-subG.R:25-108; HRS variant
-// real-data-sims.R:115-147,176-252 when hrs).
-int make_subg(int64_t n, double eps1, double eps2, double eta1, double eta2, double alpha,
-              int hrs, double lam_x, double lam_y, double lam_s, double lam_o, double lam_r,
-              double delta, int64_t nsim, SubgConst& c, double* lo_out, double* crit_sqrt2_s) {
-  std::memset(&c, 0, sizeof(c));
-  if (int st = check_common(n, eps1, eps2, alpha)) return st;
-  if (hrs && n < 2) return fail(DCOR_EINVAL, "n >= 2 required (real-data-sims.R:121)");
-  const double nd = (double)n;
-  c.n = n; c.nd = nd;
-  c.l1 = (hrs && !std::isnan(lam_x)) ? lam_x : dcor_lambda_n(nd, eta1);  // :30 / rds:123
-  c.l2 = (hrs && !std::isnan(lam_y)) ? lam_y : dcor_lambda_n(nd, eta2);
-  double md = std::ceil(8.0 / (eps1 * eps2));                            // :37
-  if (md > nd) md = nd;
-  double kd = std::floor(nd / md);                                       // :38
-  if (hrs) {
-    if (kd < 2) { kd = 2; md = std::floor(nd / kd); }                    // rds:130
-  } else if (!(kd >= 1)) {
-    return fail(DCOR_EKLT1, "correlation_NI_subG: k < 1 (ver-cor-subG.R:38)");
-  }
-  c.m = (int32_t)md; c.k = (int64_t)kd; c.md = md; c.kd = kd;
-  {
-    int e = 0;
-    c.md_pow2 = (std::frexp(md, &e) == 0.5) ? 1 : 0;
-    c.inv_md = c.md_pow2 ? std::ldexp(1.0, 1 - e) : 0.0;
-  }
-  c.bx = 2.0 * c.l1 / (md * eps1);                                       // :48
-  c.by = 2.0 * c.l2 / (md * eps2);                                       // :49
-  c.m_over_k = md / kd;                                                  // :51
-  c.crit = dcor_qnorm(1.0 - alpha / 2.0);                                // :57
-  c.sqrt_k = std::sqrt(kd);
-  c.sender_is_X = (eps1 >= eps2) ? 1 : 0;                                // :76
-  const double eps_s = c.sender_is_X ? eps1 : eps2, eps_r = c.sender_is_X ? eps2 : eps1;
-  const double eta_s = c.sender_is_X ? eta1 : eta2, eta_r = c.sender_is_X ? eta2 : eta1;
-  double lo_ = NAN;
-  if (!hrs) {
-    double lam[2];
-    dcor_lambda_int_n(nd, eta_s, eta_r, eps_s, lam);                     // :83-85
-    c.ls = lam[0]; c.lr = lam[1];
-  } else {
-    const double dl = std::isnan(delta) ? 1.0 / nd : delta;              // rds:199
-    double ls = lam_s;
-    lo_ = lam_o;
-    if (std::isnan(ls) || std::isnan(lo_)) {                             // rds:202-208
-      double lam[2];
-      dcor_lambda_int_n(nd, eta_s, eta_r, eps_s, lam);
-      if (std::isnan(ls)) ls = lam[0];
-      if (std::isnan(lo_)) lo_ = dcor_lambda_n(nd, c.sender_is_X ? eta2 : eta1);
-    }
-    double lr = lam_r;
-    if (std::isnan(lr)) lr = dcor_lambda_receiver_from_noise(ls, lo_, eps_s, dl);  // rds:211-218
-    c.ls = ls; c.lr = lr;
-  }
-  c.bs = 2.0 * c.ls / (eps_s);                                           // :89
-  c.s_central = 2.0 * c.lr / (nd * eps_r);                               // :91
-  c.sn2x2 = 2.0 * (c.s_central * c.s_central);                           // :99
-  c.sqrt_n = std::sqrt(nd);
-  c.eps_r = eps_r;
-  if (lo_out) *lo_out = lo_;
-  if (crit_sqrt2_s) *crit_sqrt2_s = c.crit * std::sqrt(2.0) * (2.0 * c.lr / (nd * eps_r));  // rds:238
-  if (int st = make_mix(nsim, alpha, c.mix)) return st;
   return DCOR_OK;
 }
 
@@ -674,14 +538,6 @@ int dcor_get_variant(const char* name, char* buf, size_t len) {
   return v.set();
 }
 
-int dcor_last_error(char* buf, size_t len) {
-  if (buf && len) {
-    std::strncpy(buf, g_err, len - 1);
-    buf[len - 1] = 0;
-  }
-  return (int)std::strlen(g_err);
-}
-
 int dcor_device_count(void) {
   if (fork_guard()) return 0;
   int n = 0;
@@ -689,78 +545,9 @@ int dcor_device_count(void) {
   return n;
 }
 
-double dcor_lambda_n(double n, double eta) {  // ver-cor-subG.R:1
-  return r_min(2.0 * eta * std::sqrt(std::log(n)), 2.0 * std::sqrt(3.0));
-}
-
-void dcor_lambda_int_n(double n, double eta_s, double eta_r, double eps_s, double out[2]) {
-  out[0] = r_min(2.0 * eta_s * std::sqrt(std::log(n)), 2.0 * std::sqrt(3.0));  // ver-cor-subG.R:4
-  out[1] = 5.0 * r_max(eta_r, 1.0) * r_min(std::log(n), 6.0) / (r_min(eps_s, 1.0));  // :5
-}
-
-double dcor_lambda_receiver_from_noise(double lam_s, double lam_o, double eps_s, double delta) {
-  const double b_s = 2.0 * lam_s / eps_s;  // real-data-sims.R:172
-  return (lam_s + b_s * std::log(1.0 / delta)) * lam_o;
-}
-
 double dcor_lambda_from_priv(double lo, double hi, double mean, double sd, double eps_sd) {
   const double sig = r_max(sd, eps_sd);  // real-data-sims.R:104
   return r_max(std::fabs((lo - mean) / sig), std::fabs((hi - mean) / sig));
-}
-
-double dcor_qnorm(double p) {
-  // R's qnorm(p, 0, 1) (qnorm.c: Wichura's AS241, lower tail, log.p = FALSE), same operation
-  // order, so crit = qnorm(1 - alpha/2) is R's double.
-  if (std::isnan(p) || p < 0 || p > 1) return NAN;
-  if (p == 0) return -INFINITY;
-  if (p == 1) return INFINITY;
-  const double q = p - 0.5;
-  double r, val;
-  if (std::fabs(q) <= .425) {
-    r = .180625 - q * q;
-    return q * (((((((r * 2509.0809287301226727 + 33430.575583588128105) * r +
-                     67265.770927008700853) * r + 45921.953931549871457) * r +
-                   13731.693765509461125) * r + 1971.5909503065514427) * r +
-                 133.14166789178437745) * r + 3.387132872796366608) /
-           (((((((r * 5226.495278852545925 + 28729.085735721942674) * r +
-                 39307.89580009271061) * r + 21213.794301586595867) * r +
-               5394.1960214247511077) * r + 687.1870074920579083) * r +
-             42.313330701600911252) * r + 1.);
-  }
-  r = std::sqrt(-std::log((q > 0) ? (0.5 - p + 0.5) : p));
-  if (r <= 5.) {
-    r += -1.6;
-    val = (((((((r * 7.7454501427834140764e-4 + .0227238449892691845833) * r +
-                .24178072517745061177) * r + 1.27045825245236838258) * r +
-              3.64784832476320460504) * r + 5.7694972214606914055) * r +
-            4.6303378461565452959) * r + 1.42343711074968357734) /
-          (((((((r * 1.05075007164441684324e-9 + 5.475938084995344946e-4) * r +
-                .0151986665636164571966) * r + .14810397642748007459) * r +
-              .68976733498510000455) * r + 1.6763848301838038494) * r +
-            2.05319162663775882187) * r + 1.);
-  } else {
-    r += -5.;
-    val = (((((((r * 2.01033439929228813265e-7 + 2.71155556874348757815e-5) * r +
-                .0012426609473880784386) * r + .026532189526576123093) * r +
-              .29656057182850489123) * r + 1.7848265399172913358) * r +
-            5.4637849111641143699) * r + 6.6579046435011037772) /
-          (((((((r * 2.04426310338993978564e-15 + 1.4215117583164458887e-7) * r +
-                1.8463183175100546818e-5) * r + 7.868691311456132591e-4) * r +
-              .0148753612908506148525) * r + .13692988092273580531) * r +
-            .59983220655588793769) * r + 1.);
-  }
-  return (q < 0.0) ? -val : val;
-}
-
-int dcor_batch_geometry(int64_t n, double eps1, double eps2, int family, int hrs, int64_t km[2]) {
-  const double nd = (double)n;
-  double md = std::ceil(8.0 / (eps1 * eps2));
-  if (family == DCOR_FAMILY_SUBG && md > nd) md = nd;
-  double kd = std::floor(nd / md);
-  if (family == DCOR_FAMILY_SUBG && hrs && kd < 2) { kd = 2; md = std::floor(nd / kd); }
-  km[0] = (int64_t)kd; km[1] = (int64_t)md;
-  if (!(kd >= 1)) return fail(DCOR_EKLT1, "k = floor(n/m) < 1");
-  return DCOR_OK;
 }
 
 // The one-pass sign path's replicate chunks: two slabs (two-stream chunk pipeline), each within a
@@ -988,38 +775,6 @@ int dcor_premat_sign_launch(const dcor_premat_sign* d, dcor_rep_out* d_out, void
   return DCOR_OK;
 }
 
-static int premat_subg_const(const dcor_premat_subg* d, PrematSubgConst& p) {
-  std::memset(&p, 0, sizeof(p));
-  if (int st = make_subg(d->n, d->eps1, d->eps2, d->eta1, d->eta2, d->alpha, d->hrs, d->lam_x,
-                         d->lam_y, d->lam_s, d->lam_o, d->lam_r, d->delta, d->nsim, p.s, &p.lo_,
-                         &p.crit_sqrt2_s)) return st;
-  p.hrs = d->hrs ? 1 : 0;
-  // element-aligned arrays (the streaming kernels read 16 B at a time from the first 16-B
-  // boundary of each row)
-  const uintptr_t mis8 = ((uintptr_t)d->X | (uintptr_t)d->Y | (uintptr_t)d->lap_ni_x |
-                          (uintptr_t)d->lap_ni_y | (uintptr_t)d->lap_local |
-                          (uintptr_t)d->lap_central | (uintptr_t)d->mix_z | (uintptr_t)d->mix_l) & 7;
-  if (mis8 || ((uintptr_t)d->perm & 3))
-    return fail(DCOR_EINVAL, "premat_subg: arrays must be aligned to their element size");
-  p.X = d->X; p.Y = d->Y; p.xy_stride = d->xy_stride; p.perm = d->perm;
-  p.lap_ni_x = d->lap_ni_x; p.lap_ni_y = d->lap_ni_y; p.lap_local = d->lap_local;
-  p.lap_central = d->lap_central; p.mix_z = d->mix_z; p.mix_l = d->mix_l;
-  return DCOR_OK;
-}
-
-struct dcor_panel {
-  const double* X;
-  const double* Y;
-  int64_t n;
-  void* buf;          // CodedPanelLayout(n)
-  dcor::CodedPanelLayout lay;
-  void* stream;
-  int coded;          // host copy of the device flag (read once at create)
-  uint16_t* codes() const { return lay.codes(buf); }
-  double* dict() const { return lay.dict(buf); }
-  int* ok() const { return lay.ok(buf); }
-};
-
 // scratch / scratch_b: a caller's stream-ordered PrematScratchLayout buffer (the sweep's), used
 // when it is large enough
 static int premat_subg_run(const dcor_premat_subg* d, const dcor_panel* panel, dcor_rep_out* d_out,
@@ -1115,14 +870,6 @@ static int premat_subg_run(const dcor_premat_subg* d, const dcor_panel* panel, d
 // launch_hrs_noise), then the pre-materialised panel kernels: the pipeline of dcor.hrs.hrs_replicates(rng='philox', mode='premat'), natively.
 // hrs_noise_geometry's per: bytes of one replicate's noise; hrs_premat_chunks runs d->reps
 // replicates in chunks of cr over the caller's stream-ordered buffer of per * cr bytes.
-static int hrs_noise_geometry(const dcor_premat_subg* d, int64_t* k, int64_t* m, size_t* per) {
-  int64_t km[2];
-  if (int st = dcor_batch_geometry(d->n, d->eps1, d->eps2, DCOR_FAMILY_SUBG, 1, km)) return st;
-  *k = km[0]; *m = km[1];
-  *per = HrsNoiseLayout(d->n, km[0], km[1], d->nsim, 1).bytes;
-  return DCOR_OK;
-}
-
 static int hrs_premat_chunks(const dcor_premat_subg* d, const dcor_panel* panel, uint64_t seed_ni,
                              uint64_t seed_int, int64_t rep_begin, dcor_rep_out* d_out, char* buf,
                              int64_t cr, int64_t k, int64_t m, void* stream,
@@ -1141,14 +888,6 @@ static int hrs_premat_chunks(const dcor_premat_subg* d, const dcor_panel* panel,
   return DCOR_OK;
 }
 
-// chunk of replicates whose noise fits `budget` bytes, capped at `cap`
-static int64_t hrs_chunk(size_t per, int64_t reps, size_t budget, int64_t cap) {
-  int64_t cr = (int64_t)(budget / per);
-  if (cr < 1) cr = 1;
-  if (cr > cap) cr = cap;
-  return cr > reps ? reps : cr;
-}
-
 // dcor_hrs_fused_launch on an uncoded panel too large for the LDS index row (n > 65536): the
 // same Philox streams materialised per chunk, then the pre-materialised panel kernels --
 // replicate r equals the fused kernel's replicate r within the compensated sums' rounding, as
@@ -1161,16 +900,9 @@ static int hrs_fused_materialised(const dcor_premat_subg* d, const dcor_panel* p
   if (int st = hrs_noise_geometry(d, &k, &m, &per)) return st;
   const int64_t cr = hrs_chunk(per, d->reps, (size_t)1 << 30, 65535);
   if (cr == 0) return DCOR_OK;
-  char* buf = nullptr;
-  const hipStream_t st = (hipStream_t)stream;
-  if (hipMallocAsync((void**)&buf, per * (size_t)cr, st) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(DCOR_ENOMEM, "hrs_fused: cannot allocate %zu noise bytes", per * (size_t)cr);
-  }
-  count_alloc();
-  const int e = hrs_premat_chunks(d, panel, seed_ni, seed_int, rep_begin, d_out, buf, cr, k, m, stream);
-  (void)hipFreeAsync(buf, st);
-  return e;
+  return with_scratch("hrs_fused", "noise", per * (size_t)cr, stream, [&](void* buf) {
+    return hrs_premat_chunks(d, panel, seed_ni, seed_int, rep_begin, d_out, (char*)buf, cr, k, m, stream);
+  });
 }
 
 int dcor_panel_create(const double* d_X, const double* d_Y, int64_t n, void* stream,
@@ -1230,6 +962,17 @@ int dcor_premat_subg_launch(const dcor_premat_subg* d, dcor_rep_out* d_out, void
   return premat_subg_run(d, nullptr, d_out, stream);
 }
 
+// A segment's constants as the fused HRS kernels take them: no materialised noise, and the
+// panel's codes when it runs coded.
+static void hrs_fused_const(PrematSubgConst& p, const dcor_panel* panel, bool coded) {
+  p.perm = nullptr; p.lap_ni_x = p.lap_ni_y = p.lap_local = p.lap_central = nullptr;
+  p.mix_z = p.mix_l = nullptr;
+  p.dict_codes = coded ? panel->codes() : nullptr;
+  p.dict_vals = coded ? panel->dict() : nullptr;
+  p.dict_ok = coded ? panel->ok() : nullptr;
+  if (coded) p.dict_built = 2;
+}
+
 int dcor_hrs_fused_launch(const dcor_premat_subg* d, const dcor_panel* panel, uint64_t seed_ni,
                           uint64_t seed_int, int64_t rep_begin, dcor_rep_out* d_out, void* stream) {
   if (!d || !panel || d->reps < 0 || (d->reps > 0 && !d_out))
@@ -1247,27 +990,14 @@ int dcor_hrs_fused_launch(const dcor_premat_subg* d, const dcor_panel* panel, ui
   const bool coded = panel->coded && !dcor::variant("DCOR_HRS_FUSED_L2").is("1");
   if (!coded && d->n > DCOR_DICT_NMAX)
     return hrs_fused_materialised(d, panel, seed_ni, seed_int, rep_begin, d_out, stream);
-  p.perm = nullptr; p.lap_ni_x = p.lap_ni_y = p.lap_local = p.lap_central = nullptr;
-  p.mix_z = p.mix_l = nullptr;
-  if (coded) {
-    p.dict_codes = panel->codes(); p.dict_vals = panel->dict(); p.dict_ok = panel->ok();
-    p.dict_built = 2;
-  } else {
-    p.dict_codes = nullptr; p.dict_vals = nullptr; p.dict_ok = nullptr;
-  }
+  hrs_fused_const(p, panel, coded);
   if (d->reps == 0) return DCOR_OK;
   const PrematScratchLayout lay(d->reps, 1, d->n, !coded, false);  // pack: the uncoded kernel's
-  void* part = nullptr;
-  if (hipMallocAsync(&part, lay.bytes, (hipStream_t)stream) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(DCOR_ENOMEM, "hrs_fused: cannot allocate %zu scratch bytes", lay.bytes);
-  }
-  count_alloc();
-  if (!coded) { p.xyc = lay.xyc(part); p.soc = lay.soc(part); }
-  const int rc = launch_hrs_fused(p, seed_ni, seed_int, rep_begin, d->reps, part, d_out, stream);
-  (void)hipFreeAsync(part, (hipStream_t)stream);
-  if (rc) return hip_fail((hipError_t)rc, "hrs_fused launch");
-  return DCOR_OK;
+  return with_scratch("hrs_fused", "scratch", lay.bytes, stream, [&](void* part) {
+    if (!coded) { p.xyc = lay.xyc(part); p.soc = lay.soc(part); }
+    const int rc = launch_hrs_fused(p, seed_ni, seed_int, rep_begin, d->reps, part, d_out, stream);
+    return rc ? hip_fail((hipError_t)rc, "hrs_fused launch") : DCOR_OK;
+  });
 }
 
 int dcor_hrs_sweep_launch(const dcor_premat_subg* base, const dcor_panel* panel,
@@ -1275,65 +1005,25 @@ int dcor_hrs_sweep_launch(const dcor_premat_subg* base, const dcor_panel* panel,
                           void* stream) {
   if (!base || !panel || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
     return fail(DCOR_EINVAL, "hrs_sweep: null argument");
-  if (base->X != panel->X || base->Y != panel->Y || base->xy_stride != 0 || base->n != panel->n)
-    return fail(DCOR_EINVAL, "hrs_sweep: X, Y, n must be the panel's and xy_stride 0");
-  if (!base->hrs) return fail(DCOR_EINVAL, "hrs_sweep: the HRS variant only (hrs = 1)");
-  if (!(base->delta > 0.0)) return fail(DCOR_EINVAL, "hrs_sweep: delta must be positive");
-  // every segment's constants and geometry first: nothing is enqueued for an invalid sweep
-  struct SegPlan {
-    dcor_premat_subg q;
-    int64_t k, m, cr;
-  };
-  std::vector<SegPlan> plan((size_t)nseg);
-  size_t need = 0;
-  int64_t cap = 0;
-  // noise of up to 8192 replicates per launch chain (C5's 8192 x 420 KB: 3.4 GB), at most 4 GB
-  const size_t budget = (size_t)4 << 30;
-  for (int64_t i = 0; i < nseg; ++i) {
-    const dcor_hrs_segment& g = segs[i];
-    if (g.reps < 0 || g.rep_begin < 0 || g.out_row < 0 || !(g.eps > 0.0))
-      return fail(DCOR_EINVAL, "hrs_sweep: segment %lld: need eps > 0, reps, rep_begin, out_row >= 0",
-                  (long long)i);
-    if (rep_range_exceeds(g.rep_begin, g.reps))
-      return fail(DCOR_EINVAL, "hrs_sweep: segment %lld: replicate range exceeds 2^32", (long long)i);
-    SegPlan& sp = plan[(size_t)i];
-    dcor_premat_subg& q = sp.q;
-    q = *base;
-    q.reps = g.reps;
-    q.eps1 = q.eps2 = g.eps;
-    q.eta1 = q.eta2 = 1.0;
-    q.lam_r = dcor_lambda_receiver_from_noise(base->lam_s, base->lam_o, g.eps, base->delta);
-    PrematSubgConst pc;   // the launch constants' own checks, here rather than mid-sweep
-    if (int st = premat_subg_const(&q, pc)) return st;
-    size_t per;
-    if (int st = hrs_noise_geometry(&q, &sp.k, &sp.m, &per)) return st;
-    sp.cr = hrs_chunk(per, g.reps, budget, 8192);
-    need = std::max(need, per * (size_t)sp.cr);
-    cap = std::max(cap, sp.cr);
-  }
-  if (need == 0) return DCOR_OK;
+  HrsSweepPlan plan;
+  if (int st = plan_hrs_sweep(base, panel, segs, nseg, plan)) return st;
+  if (plan.need == 0) return DCOR_OK;
   if (int st = need_device()) return st;
   // the premat launches' partials (80 B per replicate slice) and packed panel (uncoded: 32 B
   // per sample) follow the noise: one allocation per call, reused launch after launch in
   // stream order
-  const size_t scr_b = al256(PrematScratchLayout(cap, DCOR_DICT_SLICES, base->n, true, false).bytes);
-  char* buf = nullptr;
-  const hipStream_t st = (hipStream_t)stream;
-  if (hipMallocAsync((void**)&buf, need + scr_b, st) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(DCOR_ENOMEM, "hrs_sweep: cannot allocate %zu noise bytes", need + scr_b);
-  }
-  count_alloc();
-  int e = DCOR_OK;
-  for (int64_t i = 0; i < nseg && !e; ++i) {
-    const dcor_hrs_segment& g = segs[i];
-    const SegPlan& sp = plan[(size_t)i];
-    if (g.reps == 0) continue;
-    e = hrs_premat_chunks(&sp.q, panel, g.seed_ni, g.seed_int, g.rep_begin, d_out + g.out_row, buf,
-                          sp.cr, sp.k, sp.m, stream, buf + need, scr_b);
-  }
-  (void)hipFreeAsync(buf, st);
-  return e;
+  const size_t scr_b = al256(PrematScratchLayout(plan.cap, DCOR_DICT_SLICES, base->n, true, false).bytes);
+  return with_scratch("hrs_sweep", "noise", plan.need + scr_b, stream, [&](void* buf) {
+    int e = DCOR_OK;
+    for (int64_t i = 0; i < nseg && !e; ++i) {
+      const dcor_hrs_segment& g = segs[i];
+      const HrsSweepSeg& sp = plan.segs[(size_t)i];
+      if (g.reps == 0) continue;
+      e = hrs_premat_chunks(&sp.q, panel, g.seed_ni, g.seed_int, g.rep_begin, d_out + g.out_row,
+                            (char*)buf, sp.cr, sp.k, sp.m, stream, (char*)buf + plan.need, scr_b);
+    }
+    return e;
+  });
 }
 
 // Fused sweep scratch: partials (one SubgPartial per replicate of the call) | the segment table |
@@ -1356,103 +1046,32 @@ int dcor_hrs_fused_sweep_launch(const dcor_premat_subg* base, const dcor_panel* 
   if (!base || !panel || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
     return fail(DCOR_EINVAL, "hrs_fused_sweep: null argument");
   if (nseg == 0) return DCOR_OK;   // nothing to check against the panel, nothing to run
-  // the segments' own fields first (they need nothing but segs), then the panel and base, then
-  // every segment's launch constants: nothing is enqueued for an invalid sweep
-  int64_t items = 0;
-  for (int64_t i = 0; i < nseg; ++i) {
-    const dcor_hrs_segment& g = segs[i];
-    if (g.reps < 0 || g.rep_begin < 0 || g.out_row < 0 || !(g.eps > 0.0))
-      return fail(DCOR_EINVAL, "hrs_fused_sweep: segment %lld: need eps > 0, reps, rep_begin, out_row >= 0",
-                  (long long)i);
-    if (rep_range_exceeds(g.rep_begin, g.reps))
-      return fail(DCOR_EINVAL, "hrs_fused_sweep: segment %lld: replicate range exceeds 2^32", (long long)i);
-    items += g.reps;   // reps <= 2^32 each: no overflow below 2^31 segments
-    if (items > 0x7fffffffLL)
-      return fail(DCOR_EINVAL, "hrs_fused_sweep: more than 2^31 - 1 replicates in one call");
-  }
-  if (base->X != panel->X || base->Y != panel->Y || base->xy_stride != 0 || base->n != panel->n)
-    return fail(DCOR_EINVAL, "hrs_fused_sweep: X, Y, n must be the panel's and xy_stride 0");
-  if (!base->hrs) return fail(DCOR_EINVAL, "hrs_fused_sweep: the HRS variant only (hrs = 1)");
-  if (!(base->delta > 0.0)) return fail(DCOR_EINVAL, "hrs_fused_sweep: delta must be positive");
-  std::vector<dcor_premat_subg> qs((size_t)nseg);
-  std::vector<HrsSegConst> tab;
-  PrematSubgConst p0;      // the first segment's constants: the sweep-wide ones are read from it
-  bool wide = true;        // the sweep-wide constants are the same in every segment
-  int64_t max_km = 0, first = 0;
-  for (int64_t i = 0; i < nseg; ++i) {
-    const dcor_hrs_segment& g = segs[i];
-    dcor_premat_subg& q = qs[(size_t)i];
-    q = *base;
-    q.reps = g.reps;
-    q.eps1 = q.eps2 = g.eps;
-    q.eta1 = q.eta2 = 1.0;
-    q.lam_r = dcor_lambda_receiver_from_noise(base->lam_s, base->lam_o, g.eps, base->delta);
-    PrematSubgConst pc;
-    if (int st = premat_subg_const(&q, pc)) return st;
-    if (g.reps == 0) continue;
-    if (tab.empty()) p0 = pc;
-    const SubgConst &a = pc.s, &b = p0.s;
-    // bitwise: a NaN clip (lam_s / lam_o unset with an out-of-range eta) differs from itself in
-    // value but not as a constant
-    const double wa[] = {a.l1, a.l2, a.ls, pc.lo_, a.nd, a.sqrt_n, a.crit};
-    const double wb[] = {b.l1, b.l2, b.ls, p0.lo_, b.nd, b.sqrt_n, b.crit};
-    wide = wide && std::memcmp(wa, wb, sizeof(wa)) == 0 && a.sender_is_X == b.sender_is_X &&
-           std::memcmp(&a.mix, &b.mix, sizeof(a.mix)) == 0;
-    HrsSegConst t;
-    std::memset(&t, 0, sizeof(t));
-    t.k = a.k; t.m = a.m; t.md_pow2 = a.md_pow2;
-    t.md = a.md; t.kd = a.kd; t.inv_md = a.inv_md;
-    t.bx = a.bx; t.by = a.by; t.m_over_k = a.m_over_k; t.sqrt_k = a.sqrt_k;
-    t.lr = a.lr; t.bs = a.bs; t.s_central = a.s_central; t.sn2x2 = a.sn2x2; t.eps_r = a.eps_r;
-    t.crit_sqrt2_s = pc.crit_sqrt2_s;
-    t.ni0 = (uint32_t)g.seed_ni; t.ni1 = (uint32_t)(g.seed_ni >> 32);
-    t.in0 = (uint32_t)g.seed_int; t.in1 = (uint32_t)(g.seed_int >> 32);
-    t.rep_begin = (uint32_t)g.rep_begin;
-    t.first = first; t.out_row = g.out_row;
-    first += g.reps;
-    tab.push_back(t);
-    max_km = std::max(max_km, a.k * (int64_t)a.m);
-  }
-  if (items == 0) return DCOR_OK;
+  HrsFusedSweepPlan plan;
+  if (int st = plan_hrs_fused_sweep(base, panel, segs, nseg, plan)) return st;
+  if (plan.items == 0) return DCOR_OK;
   if (int st = need_device()) return st;
   // DCOR_HRS_FUSED_L2=1 runs a coded panel through the uncoded kernel, as in dcor_hrs_fused_launch
   const bool coded = panel->coded && !dcor::variant("DCOR_HRS_FUSED_L2").is("1");
-  if ((!coded && base->n > DCOR_DICT_NMAX) || !wide) {
+  if ((!coded && base->n > DCOR_DICT_NMAX) || !plan.wide) {
     // an uncoded panel too large for the LDS index row has no fused kernel (hrs_fused_materialised),
     // and clips that differ between segments (lam_s / lam_o unset) have no sweep-wide dictionary:
     // the segments one by one, each the per-segment entry itself
     for (int64_t i = 0; i < nseg; ++i) {
       if (segs[i].reps == 0) continue;
-      if (int e = dcor_hrs_fused_launch(&qs[(size_t)i], panel, segs[i].seed_ni, segs[i].seed_int,
+      if (int e = dcor_hrs_fused_launch(&plan.qs[(size_t)i], panel, segs[i].seed_ni, segs[i].seed_int,
                                         segs[i].rep_begin, d_out + segs[i].out_row, stream))
         return e;
     }
     return DCOR_OK;
   }
-  PrematSubgConst p = p0;
-  p.perm = nullptr; p.lap_ni_x = p.lap_ni_y = p.lap_local = p.lap_central = nullptr;
-  p.mix_z = p.mix_l = nullptr;
-  if (coded) {
-    p.dict_codes = panel->codes(); p.dict_vals = panel->dict(); p.dict_ok = panel->ok();
-    p.dict_built = 2;
-  }
-  const FusedSweepLayout lay(items, (int64_t)tab.size(), base->n, !coded);
-  void* buf = nullptr;
-  const hipStream_t st = (hipStream_t)stream;
-  if (hipMallocAsync(&buf, lay.bytes, st) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(DCOR_ENOMEM, "hrs_fused_sweep: cannot allocate %zu scratch bytes", lay.bytes);
-  }
-  count_alloc();
-  if (!coded) { p.xyc = lay.xyc(buf); p.soc = lay.soc(buf); }
-  // from pageable memory: the copy has left `tab` when the call returns
-  int rc = (int)hipMemcpyAsync(lay.tab(buf), tab.data(), tab.size() * sizeof(HrsSegConst),
-                               hipMemcpyHostToDevice, st);
-  if (!rc)
-    rc = launch_hrs_fused_sweep(p, lay.tab(buf), (int)tab.size(), items, max_km, buf, d_out, stream);
-  (void)hipFreeAsync(buf, st);
-  if (rc) return hip_fail((hipError_t)rc, "hrs_fused_sweep launch");
-  return DCOR_OK;
+  PrematSubgConst p = plan.p0;
+  hrs_fused_const(p, panel, coded);
+  const std::vector<HrsSegConst>& tab = plan.tab;
+  const FusedSweepLayout lay(plan.items, (int64_t)tab.size(), base->n, !coded);
+  return with_table("hrs_fused_sweep", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
+    if (!coded) { p.xyc = lay.xyc(buf); p.soc = lay.soc(buf); }
+    return launch_hrs_fused_sweep(p, lay.tab(buf), (int)tab.size(), plan.items, plan.max_km, buf, d_out, stream);
+  });
 }
 
 int dcor_sign_panel_launch(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs,
@@ -1460,133 +1079,33 @@ int dcor_sign_panel_launch(const dcor_sign_panel_desc* p, const dcor_sign_segmen
   if (!p || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
     return fail(DCOR_EINVAL, "sign_panel: null argument");
   if (nseg == 0) return DCOR_OK;   // nothing to run
-  if (!p->X || !p->Y) return fail(DCOR_EINVAL, "sign_panel: null argument (X, Y)");
-  // every segment's own fields, then its launch constants (n, eps, alpha, ci_mode, nsim, k >= 1:
-  // make_sign): nothing is enqueued for an invalid call
-  int64_t items = 0;
-  for (int64_t i = 0; i < nseg; ++i) {
-    const dcor_sign_segment& g = segs[i];
-    if (g.reps < 0 || g.rep_begin < 0 || g.out_row < 0 || !(g.eps1 > 0.0) || !(g.eps2 > 0.0))
-      return fail(DCOR_EINVAL, "sign_panel: segment %lld: need eps1, eps2 > 0, reps, rep_begin, out_row >= 0",
-                  (long long)i);
-    if (rep_range_exceeds(g.rep_begin, g.reps))
-      return fail(DCOR_EINVAL, "sign_panel: segment %lld: replicate range exceeds 2^32", (long long)i);
-    items += g.reps;   // reps <= 2^32 each: no overflow below 2^31 segments
-    if (items > 0x7fffffffLL)
-      return fail(DCOR_EINVAL, "sign_panel: more than 2^31 - 1 replicates in one call");
-  }
   std::vector<SignSegConst> tab;
-  int64_t first = 0;
-  for (int64_t i = 0; i < nseg; ++i) {
-    const dcor_sign_segment& g = segs[i];
-    SignSegConst t;
-    std::memset(&t, 0, sizeof(t));
-    if (int st = make_sign(p->n, g.eps1, g.eps2, p->alpha, p->normalise, p->ci_mode, p->nsim, false, t.s))
-      return st;
-    if (g.reps == 0) continue;
-    t.s.k0 = (uint32_t)g.seed; t.s.k1 = (uint32_t)(g.seed >> 32);
-    t.s.rep_begin = g.rep_begin;
-    t.first = first; t.out_row = g.out_row;
-    first += g.reps;
-    tab.push_back(t);
-  }
+  int64_t items = 0;
+  if (int st = plan_sign_panel(p, segs, nseg, tab, &items)) return st;
   if (items == 0) return DCOR_OK;
   if (int st = need_device()) return st;
   const SignPanelLayout lay((int64_t)tab.size(), p->n);
-  void* buf = nullptr;
-  const hipStream_t st = (hipStream_t)stream;
-  if (hipMallocAsync(&buf, lay.bytes, st) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(DCOR_ENOMEM, "sign_panel: cannot allocate %zu scratch bytes", lay.bytes);
-  }
-  count_alloc();
-  // from pageable memory: the copy has left `tab` when the call returns
-  int rc = (int)hipMemcpyAsync(lay.tab(buf), tab.data(), tab.size() * sizeof(SignSegConst),
-                               hipMemcpyHostToDevice, st);
-  if (!rc)
-    rc = launch_sign_panel(tab[0].s, p->X, p->Y, lay.means(buf), lay.xyc(buf), lay.tab(buf),
-                           (int)tab.size(), items, d_out, stream);
-  (void)hipFreeAsync(buf, st);
-  if (rc) return hip_fail((hipError_t)rc, "sign_panel launch");
-  return DCOR_OK;
+  return with_table("sign_panel", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
+    return launch_sign_panel(tab[0].s, p->X, p->Y, lay.means(buf), lay.xyc(buf), lay.tab(buf),
+                             (int)tab.size(), items, d_out, stream);
+  });
 }
-
-namespace {
-// The host half of dcor_sign_table_launch: every check of the call, then the device table of the
-// segments with reps > 0 in call order.  Touches no device.
-int plan_sign_table(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs, int64_t nseg,
-                    std::vector<SignPairSegConst>& tab, int64_t* items_out) {
-  if (t->p < 1 || t->p > 0x7fffffffLL)
-    return fail(DCOR_EINVAL, "sign_table: p must be in [1, 2^31) (got %lld)", (long long)t->p);
-  if (t->ld < t->n)
-    return fail(DCOR_EINVAL, "sign_table: ld = %lld < n = %lld", (long long)t->ld, (long long)t->n);
-  int64_t items = 0;
-  for (int64_t i = 0; i < nseg; ++i) {
-    const dcor_sign_pair_segment& g = segs[i];
-    if (g.reps < 0 || g.rep_begin < 0 || g.out_row < 0 || !(g.eps1 > 0.0) || !(g.eps2 > 0.0))
-      return fail(DCOR_EINVAL, "sign_table: segment %lld: need eps1, eps2 > 0, reps, rep_begin, out_row >= 0",
-                  (long long)i);
-    if (g.col_x < 0 || g.col_x >= t->p || g.col_y < 0 || g.col_y >= t->p)
-      return fail(DCOR_EINVAL, "sign_table: segment %lld: columns (%d, %d) outside [0, %lld)", (long long)i,
-                  (int)g.col_x, (int)g.col_y, (long long)t->p);
-    if (rep_range_exceeds(g.rep_begin, g.reps))
-      return fail(DCOR_EINVAL, "sign_table: segment %lld: replicate range exceeds 2^32", (long long)i);
-    items += g.reps;   // reps <= 2^32 each: no overflow below 2^31 segments
-    if (items > 0x7fffffffLL)
-      return fail(DCOR_EINVAL, "sign_table: more than 2^31 - 1 replicates in one call");
-  }
-  int64_t first = 0;
-  for (int64_t i = 0; i < nseg; ++i) {
-    const dcor_sign_pair_segment& g = segs[i];
-    SignPairSegConst s;
-    std::memset(&s, 0, sizeof(s));
-    if (int st = make_sign(t->n, g.eps1, g.eps2, t->alpha, t->normalise, t->ci_mode, t->nsim, false, s.s))
-      return st;
-    if (g.reps == 0) continue;
-    s.s.k0 = (uint32_t)g.seed; s.s.k1 = (uint32_t)(g.seed >> 32);
-    s.s.rep_begin = g.rep_begin;
-    s.first = first; s.out_row = g.out_row;
-    s.col_x = g.col_x; s.col_y = g.col_y;
-    first += g.reps;
-    tab.push_back(s);
-  }
-  // after make_sign: n is in [1, 2^31) here
-  if (!SignTableLayout((int64_t)tab.size(), t->n, t->p).ok)
-    return fail(DCOR_EINVAL, "sign_table: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)",
-                (long long)t->p, (long long)t->n);
-  *items_out = items;
-  return DCOR_OK;
-}
-}  // namespace
 
 int dcor_sign_table_launch(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream) {
   if (!t || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
     return fail(DCOR_EINVAL, "sign_table: null argument");
   if (nseg == 0) return DCOR_OK;   // nothing to run
-  if (!t->D) return fail(DCOR_EINVAL, "sign_table: null argument (D)");
   std::vector<SignPairSegConst> tab;
   int64_t items = 0;
   if (int st = plan_sign_table(t, segs, nseg, tab, &items)) return st;
   if (items == 0) return DCOR_OK;
   if (int st = need_device()) return st;
   const SignTableLayout lay((int64_t)tab.size(), t->n, t->p);
-  void* buf = nullptr;
-  const hipStream_t st = (hipStream_t)stream;
-  if (hipMallocAsync(&buf, lay.bytes, st) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(DCOR_ENOMEM, "sign_table: cannot allocate %zu scratch bytes", lay.bytes);
-  }
-  count_alloc();
-  // from pageable memory: the copy has left `tab` when the call returns
-  int rc = (int)hipMemcpyAsync(lay.tab(buf), tab.data(), tab.size() * sizeof(SignPairSegConst),
-                               hipMemcpyHostToDevice, st);
-  if (!rc)
-    rc = launch_sign_table(tab[0].s, t->D, t->p, t->ld, lay.means(buf), lay.cols(buf), lay.tab(buf),
-                           (int)tab.size(), items, d_out, stream);
-  (void)hipFreeAsync(buf, st);
-  if (rc) return hip_fail((hipError_t)rc, "sign_table launch");
-  return DCOR_OK;
+  return with_table("sign_table", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
+    return launch_sign_table(tab[0].s, t->D, t->p, t->ld, lay.means(buf), lay.cols(buf), lay.tab(buf),
+                             (int)tab.size(), items, d_out, stream);
+  });
 }
 
 int dcor_panel_dict_probe(const double* d_X, const double* d_Y, int64_t n, int* ok) {

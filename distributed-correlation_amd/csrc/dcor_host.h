@@ -1,6 +1,7 @@
 // dcor_host.h -- host-side internals shared by the C-ABI translation units (dcor_capi.cpp,
-// dcor_grid.cpp): error reporting, the per-(thread, device) library context, and the per-cell
-// constant builder.  Not part of the ABI.
+// dcor_grid.cpp) that need HIP types: HIP error reporting, the per-(thread, device) library
+// context, and the per-cell constant builder.  Everything that needs no device is dcor_plan.h's.
+// Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,13 +11,12 @@
 
 #include "../../include/dcor.h"
 #include "dcor_engine.h"
+#include "dcor_plan.h"
 
 namespace dcor {
 struct SignPartial;
 namespace host {
 
-// Record the message of a failure for dcor_last_error() (thread-local) and return `code`.
-int fail(int code, const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 #define HIPCHK(expr)                                   \
   do {                                                 \
@@ -26,12 +26,6 @@ int hip_fail(hipError_t e, const char* what);
 
 // DCOR_EFORK in a process forked after its parent used the engine, DCOR_ENODEV without a GPU.
 int need_device();
-// Replicate indices are 32-bit Philox counters: for rep_begin >= 0 and reps >= 0 (the caller
-// checks), true when rep_begin + reps > 2^32 - 1 -- without forming the sum, which overflows for
-// a huge rep_begin.
-inline bool rep_range_exceeds(int64_t rep_begin, int64_t reps) { return rep_begin > 0xffffffffLL - reps; }
-double r_min(double a, double b);
-double r_max(double a, double b);
 
 struct Arena { void* p = nullptr; size_t bytes = 0; };
 // s: the auxiliary stream of the two-stream pipelines (fork / join with the caller's stream).  The

@@ -1,0 +1,476 @@
+// dcor_plan.cpp -- the device-free half of the host side (dcor_plan.h): the error reporter, the
+// argument checks of the reference's stopifnot() calls, every data-independent scalar of the
+// estimators (R operation order, cited), and the segment planners of the four segment-list
+// entries.  No HIP: this file and the headers it includes compile with a host compiler alone.
+#include "dcor_plan.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+
+namespace dcor {
+namespace host {
+
+thread_local char g_err[512] = "";
+
+int fail(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+double r_min(double a, double b) { return (std::isnan(a) || std::isnan(b)) ? NAN : (a < b ? a : b); }
+double r_max(double a, double b) { return (std::isnan(a) || std::isnan(b)) ? NAN : (a > b ? a : b); }
+
+// T with (double)w * 2^-32 < p  <=>  w < T for every uint32 w: T = ceil(p * 2^32) clamped
+// to [0, 2^32] (p * 2^32 is exact).
+uint64_t u32_threshold(double p) {
+  if (!(p > 0)) return 0;
+  const double t = std::ceil(p * 4294967296.0);
+  return t >= 4294967296.0 ? (uint64_t)4294967296ull : (uint64_t)t;
+}
+
+// MixConst for sort(x)[ceiling(p*nsim)], p = 1 - alpha/2.
+int make_mix(int64_t nsim, double alpha, MixConst& mx) {
+  if (nsim < 1 || nsim > 2048) return fail(DCOR_EINVAL, "nsim must be in [1, 2048] (got %lld)", (long long)nsim);
+  const double pos = std::ceil((1.0 - alpha / 2.0) * (double)nsim);
+  mx.nsim = (int32_t)nsim;
+  mx.pos = (pos >= 1 && pos <= (double)nsim) ? (int32_t)pos - 1 : -1;
+  mx.P = 1;
+  while (mx.P < mx.nsim) mx.P <<= 1;
+  mx.pad = 0;
+  return DCOR_OK;
+}
+
+int check_common(int64_t n, double eps1, double eps2, double alpha) {
+  if (n < 1 || n > 0x7fffffffLL) return fail(DCOR_EINVAL, "n must be in [1, 2^31) (got %lld)", (long long)n);
+  if (!(eps1 > 0) || !(eps2 > 0) || !std::isfinite(eps1) || !std::isfinite(eps2))
+    return fail(DCOR_EINVAL, "eps1 > 0 and eps2 > 0 required (vert-cor.R:264)");
+  // The reference never checks alpha: qnorm(1 - alpha/2) and mixquant's
+  // sort(x)[ceiling((1 - alpha/2) nsim)] are evaluated as they come (alpha = 1: a zero-width
+  // CI; alpha < 0: NaN).  alpha >= 2 makes the mixquant index < 1, where R's x[0] is
+  // numeric(0) and run_sim_one's detail assignment fails, so it is refused here.
+  if (std::isnan(alpha) || !(alpha < 2))
+    return fail(DCOR_EINVAL, "alpha must be < 2 (R's mixquant index ceiling((1-alpha/2)*nsim) >= 1)");
+  return DCOR_OK;
+}
+
+// ci_NI_signbatch + ci_INT_signflip scalars (vert-cor.R:204-317).
+// allow_k0: INT-only single calls (ci_INT_signflip has no batch requirement).
+int make_sign(int64_t n, double eps1, double eps2, double alpha, int normalise, int mode,
+              int64_t nsim, bool allow_k0, SignConst& c) {
+  std::memset(&c, 0, sizeof(c));
+  if (int st = check_common(n, eps1, eps2, alpha)) return st;
+  const double nd = (double)n;
+  const double md = std::ceil(8.0 / (eps1 * eps2));                     // :207
+  const double kd = std::floor(nd / md);                                 // :208
+  if (!(kd >= 1) && !allow_k0)
+    return fail(DCOR_EKLT1, "ci_NI_signbatch: k = floor(n/m) = %g < 1 (n=%lld, m=%g; vert-cor.R:209)", kd, (long long)n, md);
+  if (md > 0x7fffffff) return fail(DCOR_EINVAL, "batch size m too large");
+  c.n = n; c.m = (int32_t)md; c.k = kd >= 1 ? (int64_t)kd : 0;
+  c.nd = nd; c.md = md; c.kd = kd;
+  c.pieces = sign_pieces(c.m);
+  {
+    int e = 0;
+    c.md_pow2 = (std::frexp(md, &e) == 0.5) ? 1 : 0;  // md = 2^(e-1): count / md == count * 2^(1-e)
+    c.inv_md = c.md_pow2 ? std::ldexp(1.0, 1 - e) : 0.0;
+  }
+  c.normalise = normalise ? 1 : 0;
+  const double L = std::sqrt(2.0 * std::log(nd));                        // :212
+  c.L = L;
+  c.s_mu_x = 2.0 * L / (nd * (eps1 / 2));                                // :335-336
+  c.s_m2_x = 2.0 * (L * L) / (nd * (eps1 / 2));                          // :339-340
+  c.s_mu_y = 2.0 * L / (nd * (eps2 / 2));
+  c.s_m2_y = 2.0 * (L * L) / (nd * (eps2 / 2));
+  c.bx = 2.0 / (md * eps1);                                              // :230
+  c.by = 2.0 / (md * eps2);                                              // :231
+  c.inv_k = 1.0 / kd;                                                    // :234
+  c.crit = dcor_qnorm(1.0 - alpha / 2.0);                                // :242
+  c.sqrt_k = std::sqrt(kd);
+  c.sender_is_X = (eps1 >= eps2) ? 1 : 0;                                // :275
+  const double eps_s = c.sender_is_X ? eps1 : eps2, eps_r = c.sender_is_X ? eps2 : eps1;
+  const double es = std::exp(eps_s);
+  c.pflip = es / (es + 1.0);                                             // :174
+  c.flipT = u32_threshold(c.pflip);
+  {
+    const double t = std::ceil(c.pflip * 16777216.0);  // exact scaling
+    c.flipT24 = t >= 16777216.0 ? 16777216u : (t > 0 ? (uint32_t)t : 0u);
+  }
+  c.scale_Z = 2.0 * (es + 1.0) / (nd * (es - 1.0) * eps_r);              // :186-187
+  c.coefZ = (es + 1.0) / (nd * (es - 1.0));                              // :190-191
+  const double q = (es - 1.0) / (es + 1.0);
+  c.q2 = q * q;                                                          // :284
+  c.ratio = (es + 1.0) / (es - 1.0);                                     // :289
+  c.inv_sqrt_n = 1.0 / std::sqrt(nd);
+  c.eps_r = eps_r;
+  c.w_laplace = (2.0 / (nd * eps_r)) * c.ratio * std::log(1.0 / alpha);  // :305-308
+  int md_ = mode;
+  if (md_ == DCOR_MODE_AUTO) md_ = (std::sqrt(nd) * eps_r > 0.5) ? DCOR_MODE_NORMAL : DCOR_MODE_LAPLACE;  // :294-296
+  else if (md_ != DCOR_MODE_NORMAL && md_ != DCOR_MODE_LAPLACE) return fail(DCOR_EINVAL, "ci_mode must be auto/normal/laplace");
+  c.mode_normal = (md_ == DCOR_MODE_NORMAL) ? 1 : 0;
+  if (int st = make_mix(nsim, alpha, c.mix)) return st;
+  return DCOR_OK;
+}
+
+// correlation_NI_subG + ci_INT_subG scalars (ver-cor-subG.R:25-108; HRS variant
+// real-data-sims.R:115-147,176-252 when hrs).
+int make_subg(int64_t n, double eps1, double eps2, double eta1, double eta2, double alpha,
+              int hrs, double lam_x, double lam_y, double lam_s, double lam_o, double lam_r,
+              double delta, int64_t nsim, SubgConst& c, double* lo_out, double* crit_sqrt2_s) {
+  std::memset(&c, 0, sizeof(c));
+  if (int st = check_common(n, eps1, eps2, alpha)) return st;
+  if (hrs && n < 2) return fail(DCOR_EINVAL, "n >= 2 required (real-data-sims.R:121)");
+  const double nd = (double)n;
+  c.n = n; c.nd = nd;
+  c.l1 = (hrs && !std::isnan(lam_x)) ? lam_x : dcor_lambda_n(nd, eta1);  // :30 / rds:123
+  c.l2 = (hrs && !std::isnan(lam_y)) ? lam_y : dcor_lambda_n(nd, eta2);
+  double md = std::ceil(8.0 / (eps1 * eps2));                            // :37
+  if (md > nd) md = nd;
+  double kd = std::floor(nd / md);                                       // :38
+  if (hrs) {
+    if (kd < 2) { kd = 2; md = std::floor(nd / kd); }                    // rds:130
+  } else if (!(kd >= 1)) {
+    return fail(DCOR_EKLT1, "correlation_NI_subG: k < 1 (ver-cor-subG.R:38)");
+  }
+  c.m = (int32_t)md; c.k = (int64_t)kd; c.md = md; c.kd = kd;
+  {
+    int e = 0;
+    c.md_pow2 = (std::frexp(md, &e) == 0.5) ? 1 : 0;
+    c.inv_md = c.md_pow2 ? std::ldexp(1.0, 1 - e) : 0.0;
+  }
+  c.bx = 2.0 * c.l1 / (md * eps1);                                       // :48
+  c.by = 2.0 * c.l2 / (md * eps2);                                       // :49
+  c.m_over_k = md / kd;                                                  // :51
+  c.crit = dcor_qnorm(1.0 - alpha / 2.0);                                // :57
+  c.sqrt_k = std::sqrt(kd);
+  c.sender_is_X = (eps1 >= eps2) ? 1 : 0;                                // :76
+  const double eps_s = c.sender_is_X ? eps1 : eps2, eps_r = c.sender_is_X ? eps2 : eps1;
+  const double eta_s = c.sender_is_X ? eta1 : eta2, eta_r = c.sender_is_X ? eta2 : eta1;
+  double lo_ = NAN;
+  if (!hrs) {
+    double lam[2];
+    dcor_lambda_int_n(nd, eta_s, eta_r, eps_s, lam);                     // :83-85
+    c.ls = lam[0]; c.lr = lam[1];
+  } else {
+    const double dl = std::isnan(delta) ? 1.0 / nd : delta;              // rds:199
+    double ls = lam_s;
+    lo_ = lam_o;
+    if (std::isnan(ls) || std::isnan(lo_)) {                             // rds:202-208
+      double lam[2];
+      dcor_lambda_int_n(nd, eta_s, eta_r, eps_s, lam);
+      if (std::isnan(ls)) ls = lam[0];
+      if (std::isnan(lo_)) lo_ = dcor_lambda_n(nd, c.sender_is_X ? eta2 : eta1);
+    }
+    double lr = lam_r;
+    if (std::isnan(lr)) lr = dcor_lambda_receiver_from_noise(ls, lo_, eps_s, dl);  // rds:211-218
+    c.ls = ls; c.lr = lr;
+  }
+  c.bs = 2.0 * c.ls / (eps_s);                                           // :89
+  c.s_central = 2.0 * c.lr / (nd * eps_r);                               // :91
+  c.sn2x2 = 2.0 * (c.s_central * c.s_central);                           // :99
+  c.sqrt_n = std::sqrt(nd);
+  c.eps_r = eps_r;
+  if (lo_out) *lo_out = lo_;
+  if (crit_sqrt2_s) *crit_sqrt2_s = c.crit * std::sqrt(2.0) * (2.0 * c.lr / (nd * eps_r));  // rds:238
+  if (int st = make_mix(nsim, alpha, c.mix)) return st;
+  return DCOR_OK;
+}
+
+int premat_subg_const(const dcor_premat_subg* d, PrematSubgConst& p) {
+  std::memset(&p, 0, sizeof(p));
+  if (int st = make_subg(d->n, d->eps1, d->eps2, d->eta1, d->eta2, d->alpha, d->hrs, d->lam_x,
+                         d->lam_y, d->lam_s, d->lam_o, d->lam_r, d->delta, d->nsim, p.s, &p.lo_,
+                         &p.crit_sqrt2_s)) return st;
+  p.hrs = d->hrs ? 1 : 0;
+  // element-aligned arrays (the streaming kernels read 16 B at a time from the first 16-B
+  // boundary of each row)
+  const uintptr_t mis8 = ((uintptr_t)d->X | (uintptr_t)d->Y | (uintptr_t)d->lap_ni_x |
+                          (uintptr_t)d->lap_ni_y | (uintptr_t)d->lap_local |
+                          (uintptr_t)d->lap_central | (uintptr_t)d->mix_z | (uintptr_t)d->mix_l) & 7;
+  if (mis8 || ((uintptr_t)d->perm & 3))
+    return fail(DCOR_EINVAL, "premat_subg: arrays must be aligned to their element size");
+  p.X = d->X; p.Y = d->Y; p.xy_stride = d->xy_stride; p.perm = d->perm;
+  p.lap_ni_x = d->lap_ni_x; p.lap_ni_y = d->lap_ni_y; p.lap_local = d->lap_local;
+  p.lap_central = d->lap_central; p.mix_z = d->mix_z; p.mix_l = d->mix_l;
+  return DCOR_OK;
+}
+
+int hrs_noise_geometry(const dcor_premat_subg* d, int64_t* k, int64_t* m, size_t* per) {
+  int64_t km[2];
+  if (int st = dcor_batch_geometry(d->n, d->eps1, d->eps2, DCOR_FAMILY_SUBG, 1, km)) return st;
+  *k = km[0]; *m = km[1];
+  *per = HrsNoiseLayout(d->n, km[0], km[1], d->nsim, 1).bytes;
+  return DCOR_OK;
+}
+
+int64_t hrs_chunk(size_t per, int64_t reps, size_t budget, int64_t cap) {
+  int64_t cr = (int64_t)(budget / per);
+  if (cr < 1) cr = 1;
+  if (cr > cap) cr = cap;
+  return cr > reps ? reps : cr;
+}
+
+// ------------------------------------------------------------------ segment planners
+namespace {
+
+// What the three segment types differ in: the name(s) of eps, and the table's columns.
+template <class Seg> bool eps_ok(const Seg& g) { return g.eps1 > 0.0 && g.eps2 > 0.0; }
+bool eps_ok(const dcor_hrs_segment& g) { return g.eps > 0.0; }
+template <class Seg> const char* eps_names(const Seg&) { return "eps1, eps2"; }
+const char* eps_names(const dcor_hrs_segment&) { return "eps"; }
+template <class Seg> int check_columns(const char*, const Seg&, int64_t, int64_t) { return DCOR_OK; }
+int check_columns(const char* entry, const dcor_sign_pair_segment& g, int64_t i, int64_t p) {
+  if (g.col_x < 0 || g.col_x >= p || g.col_y < 0 || g.col_y >= p)
+    return fail(DCOR_EINVAL, "%s: segment %lld: columns (%d, %d) outside [0, %lld)", entry, (long long)i,
+                (int)g.col_x, (int)g.col_y, (long long)p);
+  return DCOR_OK;
+}
+void set_columns(SignSegConst&, const dcor_sign_segment&) {}
+void set_columns(SignPairSegConst& t, const dcor_sign_pair_segment& g) { t.col_x = g.col_x; t.col_y = g.col_y; }
+
+// Segment i's own fields (they need nothing but the segment; p: the table's column count), its
+// replicates added to `items`; cap: at most 2^31 - 1 replicates in one call.
+template <class Seg>
+int segment_head(const char* entry, const Seg& g, int64_t i, int64_t p, bool cap, int64_t& items) {
+  if (g.reps < 0 || g.rep_begin < 0 || g.out_row < 0 || !eps_ok(g))
+    return fail(DCOR_EINVAL, "%s: segment %lld: need %s > 0, reps, rep_begin, out_row >= 0", entry,
+                (long long)i, eps_names(g));
+  if (int st = check_columns(entry, g, i, p)) return st;
+  if (rep_range_exceeds(g.rep_begin, g.reps))
+    return fail(DCOR_EINVAL, "%s: segment %lld: replicate range exceeds 2^32", entry, (long long)i);
+  items += g.reps;   // reps <= 2^32 each: no overflow below 2^31 segments
+  if (cap && items > 0x7fffffffLL)
+    return fail(DCOR_EINVAL, "%s: more than 2^31 - 1 replicates in one call", entry);
+  return DCOR_OK;
+}
+
+template <class Seg>
+int segment_heads(const char* entry, const Seg* segs, int64_t nseg, int64_t p, int64_t* items) {
+  *items = 0;
+  for (int64_t i = 0; i < nseg; ++i)
+    if (int st = segment_head(entry, segs[i], i, p, true, *items)) return st;
+  return DCOR_OK;
+}
+
+// Every segment's launch constants (n, eps, alpha, ci_mode, nsim, k >= 1: make_sign; a segment
+// without replicates is checked too), the kept ones into `tab`.
+template <class Desc, class Seg, class SegConst>
+int sign_segment_table(const Desc& d, const Seg* segs, int64_t nseg, std::vector<SegConst>& tab) {
+  int64_t first = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const Seg& g = segs[i];
+    SegConst t;
+    std::memset(&t, 0, sizeof(t));
+    if (int st = make_sign(d.n, g.eps1, g.eps2, d.alpha, d.normalise, d.ci_mode, d.nsim, false, t.s))
+      return st;
+    if (g.reps == 0) continue;
+    t.s.k0 = (uint32_t)g.seed; t.s.k1 = (uint32_t)(g.seed >> 32);
+    t.s.rep_begin = g.rep_begin;
+    t.first = first; t.out_row = g.out_row;
+    set_columns(t, g);
+    first += g.reps;
+    tab.push_back(t);
+  }
+  return DCOR_OK;
+}
+
+// The panel and base checks of the two HRS sweeps.
+int check_hrs_base(const char* entry, const dcor_premat_subg* base, const dcor_panel* panel) {
+  if (base->X != panel->X || base->Y != panel->Y || base->xy_stride != 0 || base->n != panel->n)
+    return fail(DCOR_EINVAL, "%s: X, Y, n must be the panel's and xy_stride 0", entry);
+  if (!base->hrs) return fail(DCOR_EINVAL, "%s: the HRS variant only (hrs = 1)", entry);
+  if (!(base->delta > 0.0)) return fail(DCOR_EINVAL, "%s: delta must be positive", entry);
+  return DCOR_OK;
+}
+
+}  // namespace
+
+dcor_premat_subg hrs_segment_desc(const dcor_premat_subg& base, const dcor_hrs_segment& g) {
+  dcor_premat_subg q = base;
+  q.reps = g.reps;
+  q.eps1 = q.eps2 = g.eps;
+  q.eta1 = q.eta2 = 1.0;
+  q.lam_r = dcor_lambda_receiver_from_noise(base.lam_s, base.lam_o, g.eps, base.delta);
+  return q;
+}
+
+int plan_hrs_sweep(const dcor_premat_subg* base, const dcor_panel* panel,
+                   const dcor_hrs_segment* segs, int64_t nseg, HrsSweepPlan& plan) {
+  if (int st = check_hrs_base("hrs_sweep", base, panel)) return st;
+  // every segment's constants and geometry first: nothing is enqueued for an invalid sweep
+  plan.segs = std::vector<HrsSweepSeg>((size_t)nseg);
+  // noise of up to 8192 replicates per launch chain (C5's 8192 x 420 KB: 3.4 GB), at most 4 GB
+  const size_t budget = (size_t)4 << 30;
+  int64_t items = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_hrs_segment& g = segs[i];
+    if (int st = segment_head("hrs_sweep", g, i, 0, false, items)) return st;
+    HrsSweepSeg& sp = plan.segs[(size_t)i];
+    sp.q = hrs_segment_desc(*base, g);
+    PrematSubgConst pc;   // the launch constants' own checks, here rather than mid-sweep
+    if (int st = premat_subg_const(&sp.q, pc)) return st;
+    size_t per;
+    if (int st = hrs_noise_geometry(&sp.q, &sp.k, &sp.m, &per)) return st;
+    sp.cr = hrs_chunk(per, g.reps, budget, 8192);
+    plan.need = std::max(plan.need, per * (size_t)sp.cr);
+    plan.cap = std::max(plan.cap, sp.cr);
+  }
+  return DCOR_OK;
+}
+
+int plan_hrs_fused_sweep(const dcor_premat_subg* base, const dcor_panel* panel,
+                         const dcor_hrs_segment* segs, int64_t nseg, HrsFusedSweepPlan& plan) {
+  // the segments' own fields first (they need nothing but segs), then the panel and base, then
+  // every segment's launch constants: nothing is enqueued for an invalid sweep
+  if (int st = segment_heads("hrs_fused_sweep", segs, nseg, 0, &plan.items)) return st;
+  if (int st = check_hrs_base("hrs_fused_sweep", base, panel)) return st;
+  plan.qs = std::vector<dcor_premat_subg>((size_t)nseg);
+  std::vector<HrsSegConst>& tab = plan.tab;
+  PrematSubgConst& p0 = plan.p0;
+  int64_t first = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_hrs_segment& g = segs[i];
+    dcor_premat_subg& q = plan.qs[(size_t)i];
+    q = hrs_segment_desc(*base, g);
+    PrematSubgConst pc;
+    if (int st = premat_subg_const(&q, pc)) return st;
+    if (g.reps == 0) continue;
+    if (tab.empty()) p0 = pc;
+    const SubgConst &a = pc.s, &b = p0.s;
+    // bitwise: a NaN clip (lam_s / lam_o unset with an out-of-range eta) differs from itself in
+    // value but not as a constant
+    const double wa[] = {a.l1, a.l2, a.ls, pc.lo_, a.nd, a.sqrt_n, a.crit};
+    const double wb[] = {b.l1, b.l2, b.ls, p0.lo_, b.nd, b.sqrt_n, b.crit};
+    plan.wide = plan.wide && std::memcmp(wa, wb, sizeof(wa)) == 0 && a.sender_is_X == b.sender_is_X &&
+                std::memcmp(&a.mix, &b.mix, sizeof(a.mix)) == 0;
+    HrsSegConst t;
+    std::memset(&t, 0, sizeof(t));
+    t.k = a.k; t.m = a.m; t.md_pow2 = a.md_pow2;
+    t.md = a.md; t.kd = a.kd; t.inv_md = a.inv_md;
+    t.bx = a.bx; t.by = a.by; t.m_over_k = a.m_over_k; t.sqrt_k = a.sqrt_k;
+    t.lr = a.lr; t.bs = a.bs; t.s_central = a.s_central; t.sn2x2 = a.sn2x2; t.eps_r = a.eps_r;
+    t.crit_sqrt2_s = pc.crit_sqrt2_s;
+    t.ni0 = (uint32_t)g.seed_ni; t.ni1 = (uint32_t)(g.seed_ni >> 32);
+    t.in0 = (uint32_t)g.seed_int; t.in1 = (uint32_t)(g.seed_int >> 32);
+    t.rep_begin = (uint32_t)g.rep_begin;
+    t.first = first; t.out_row = g.out_row;
+    first += g.reps;
+    tab.push_back(t);
+    plan.max_km = std::max(plan.max_km, a.k * (int64_t)a.m);
+  }
+  return DCOR_OK;
+}
+
+int plan_sign_panel(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs, int64_t nseg,
+                    std::vector<SignSegConst>& tab, int64_t* items) {
+  if (!p->X || !p->Y) return fail(DCOR_EINVAL, "sign_panel: null argument (X, Y)");
+  if (int st = segment_heads("sign_panel", segs, nseg, 0, items)) return st;
+  return sign_segment_table(*p, segs, nseg, tab);
+}
+
+int plan_sign_table(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs, int64_t nseg,
+                    std::vector<SignPairSegConst>& tab, int64_t* items) {
+  if (!t->D) return fail(DCOR_EINVAL, "sign_table: null argument (D)");
+  if (t->p < 1 || t->p > 0x7fffffffLL)
+    return fail(DCOR_EINVAL, "sign_table: p must be in [1, 2^31) (got %lld)", (long long)t->p);
+  if (t->ld < t->n)
+    return fail(DCOR_EINVAL, "sign_table: ld = %lld < n = %lld", (long long)t->ld, (long long)t->n);
+  if (int st = segment_heads("sign_table", segs, nseg, t->p, items)) return st;
+  if (int st = sign_segment_table(*t, segs, nseg, tab)) return st;
+  // after make_sign: n is in [1, 2^31) here
+  if (!SignTableLayout((int64_t)tab.size(), t->n, t->p).ok)
+    return fail(DCOR_EINVAL, "sign_table: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)",
+                (long long)t->p, (long long)t->n);
+  return DCOR_OK;
+}
+
+}  // namespace host
+}  // namespace dcor
+
+// ===================================================================== ABI
+using namespace dcor::host;
+
+extern "C" {
+
+int dcor_last_error(char* buf, size_t len) {
+  if (buf && len) {
+    std::strncpy(buf, g_err, len - 1);
+    buf[len - 1] = 0;
+  }
+  return (int)std::strlen(g_err);
+}
+
+double dcor_lambda_n(double n, double eta) {  // ver-cor-subG.R:1
+  return r_min(2.0 * eta * std::sqrt(std::log(n)), 2.0 * std::sqrt(3.0));
+}
+
+void dcor_lambda_int_n(double n, double eta_s, double eta_r, double eps_s, double out[2]) {
+  out[0] = r_min(2.0 * eta_s * std::sqrt(std::log(n)), 2.0 * std::sqrt(3.0));  // ver-cor-subG.R:4
+  out[1] = 5.0 * r_max(eta_r, 1.0) * r_min(std::log(n), 6.0) / (r_min(eps_s, 1.0));  // :5
+}
+
+double dcor_lambda_receiver_from_noise(double lam_s, double lam_o, double eps_s, double delta) {
+  const double b_s = 2.0 * lam_s / eps_s;  // real-data-sims.R:172
+  return (lam_s + b_s * std::log(1.0 / delta)) * lam_o;
+}
+
+double dcor_qnorm(double p) {
+  // R's qnorm(p, 0, 1) (qnorm.c: Wichura's AS241, lower tail, log.p = FALSE), same operation
+  // order, so crit = qnorm(1 - alpha/2) is R's double.
+  if (std::isnan(p) || p < 0 || p > 1) return NAN;
+  if (p == 0) return -INFINITY;
+  if (p == 1) return INFINITY;
+  const double q = p - 0.5;
+  double r, val;
+  if (std::fabs(q) <= .425) {
+    r = .180625 - q * q;
+    return q * (((((((r * 2509.0809287301226727 + 33430.575583588128105) * r +
+                     67265.770927008700853) * r + 45921.953931549871457) * r +
+                   13731.693765509461125) * r + 1971.5909503065514427) * r +
+                 133.14166789178437745) * r + 3.387132872796366608) /
+           (((((((r * 5226.495278852545925 + 28729.085735721942674) * r +
+                 39307.89580009271061) * r + 21213.794301586595867) * r +
+               5394.1960214247511077) * r + 687.1870074920579083) * r +
+             42.313330701600911252) * r + 1.);
+  }
+  r = std::sqrt(-std::log((q > 0) ? (0.5 - p + 0.5) : p));
+  if (r <= 5.) {
+    r += -1.6;
+    val = (((((((r * 7.7454501427834140764e-4 + .0227238449892691845833) * r +
+                .24178072517745061177) * r + 1.27045825245236838258) * r +
+              3.64784832476320460504) * r + 5.7694972214606914055) * r +
+            4.6303378461565452959) * r + 1.42343711074968357734) /
+          (((((((r * 1.05075007164441684324e-9 + 5.475938084995344946e-4) * r +
+                .0151986665636164571966) * r + .14810397642748007459) * r +
+              .68976733498510000455) * r + 1.6763848301838038494) * r +
+            2.05319162663775882187) * r + 1.);
+  } else {
+    r += -5.;
+    val = (((((((r * 2.01033439929228813265e-7 + 2.71155556874348757815e-5) * r +
+                .0012426609473880784386) * r + .026532189526576123093) * r +
+              .29656057182850489123) * r + 1.7848265399172913358) * r +
+            5.4637849111641143699) * r + 6.6579046435011037772) /
+          (((((((r * 2.04426310338993978564e-15 + 1.4215117583164458887e-7) * r +
+                1.8463183175100546818e-5) * r + 7.868691311456132591e-4) * r +
+              .0148753612908506148525) * r + .13692988092273580531) * r +
+            .59983220655588793769) * r + 1.);
+  }
+  return (q < 0.0) ? -val : val;
+}
+
+int dcor_batch_geometry(int64_t n, double eps1, double eps2, int family, int hrs, int64_t km[2]) {
+  const double nd = (double)n;
+  double md = std::ceil(8.0 / (eps1 * eps2));
+  if (family == DCOR_FAMILY_SUBG && md > nd) md = nd;
+  double kd = std::floor(nd / md);
+  if (family == DCOR_FAMILY_SUBG && hrs && kd < 2) { kd = 2; md = std::floor(nd / kd); }
+  km[0] = (int64_t)kd; km[1] = (int64_t)md;
+  if (!(kd >= 1)) return fail(DCOR_EKLT1, "k = floor(n/m) < 1");
+  return DCOR_OK;
+}
+
+}  // extern "C"

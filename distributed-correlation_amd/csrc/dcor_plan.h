@@ -1,0 +1,118 @@
+// dcor_plan.h -- the host decisions that need no device: the error reporter, the argument checks,
+// every launch constant (R operation order, cited) and the segment planners of the four
+// segment-list entries.  Plain C++: neither this header nor dcor_plan.cpp includes the HIP
+// runtime, so the unit compiles, runs and is sanitized with a host compiler alone
+// (tests/host/plan_check.cpp).  Not part of the ABI.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+// dcor_engine.h names two things of the HIP headers: double2 (by pointer, and by size in the
+// scratch layouts) and the __host__ __device__ markers.  Where the HIP headers have not been read
+// (this unit, the stand-alone test program) they are stand-ins of HIP's size and alignment.
+#ifndef HIP_INCLUDE_HIP_HIP_VECTOR_TYPES_H
+struct alignas(16) double2 { double x, y; };
+#endif
+#ifndef __host__
+#define __host__
+#define __device__
+#endif
+
+#include "../../include/dcor.h"
+#include "dcor_engine.h"
+
+static_assert(sizeof(double2) == 16 && alignof(double2) == 16, "the scratch layouts' pack stride");
+
+// A prepared HRS panel (dcor_panel_create): plain data, defined here so the HRS planners can check
+// a sweep against its panel without reading the panel before the segments' own fields.
+struct dcor_panel {
+  const double* X;
+  const double* Y;
+  int64_t n;
+  void* buf;          // CodedPanelLayout(n)
+  dcor::CodedPanelLayout lay;
+  void* stream;
+  int coded;          // host copy of the device flag (read once at create)
+  uint16_t* codes() const { return lay.codes(buf); }
+  double* dict() const { return lay.dict(buf); }
+  int* ok() const { return lay.ok(buf); }
+};
+
+namespace dcor {
+namespace host {
+
+// Record the message of a failure for dcor_last_error() (thread-local) and return `code`.
+int fail(int code, const char* fmt, ...);
+// Replicate indices are 32-bit Philox counters: for rep_begin >= 0 and reps >= 0 (the caller
+// checks), true when rep_begin + reps > 2^32 - 1 -- without forming the sum, which overflows for
+// a huge rep_begin.
+inline bool rep_range_exceeds(int64_t rep_begin, int64_t reps) { return rep_begin > 0xffffffffLL - reps; }
+double r_min(double a, double b);
+double r_max(double a, double b);
+// T with (double)w * 2^-32 < p  <=>  w < T for every uint32 w
+uint64_t u32_threshold(double p);
+
+// The launch constants of the estimators; each returns the status the reference raises.
+int check_common(int64_t n, double eps1, double eps2, double alpha);
+int make_mix(int64_t nsim, double alpha, MixConst& mx);
+int make_sign(int64_t n, double eps1, double eps2, double alpha, int normalise, int mode,
+              int64_t nsim, bool allow_k0, SignConst& c);
+int make_subg(int64_t n, double eps1, double eps2, double eta1, double eta2, double alpha,
+              int hrs, double lam_x, double lam_y, double lam_s, double lam_o, double lam_r,
+              double delta, int64_t nsim, SubgConst& c, double* lo_out, double* crit_sqrt2_s);
+
+// What follows is new with the planning unit and stays out of the library's dynamic symbols.
+#pragma GCC visibility push(hidden)
+
+int premat_subg_const(const dcor_premat_subg* d, PrematSubgConst& p);
+// per: bytes of one HRS replicate's materialised noise; hrs_chunk: the replicates whose noise
+// fits `budget` bytes, capped at `cap`
+int hrs_noise_geometry(const dcor_premat_subg* d, int64_t* k, int64_t* m, size_t* per);
+int64_t hrs_chunk(size_t per, int64_t reps, size_t budget, int64_t cap);
+
+// ---- the segment planners: every check of an entry after its null checks, in the entry's order,
+// then its table of the segments with reps > 0 in call order.  None touches a device. ----
+
+// The sweep's descriptor at one segment's eps (both HRS sweeps).
+dcor_premat_subg hrs_segment_desc(const dcor_premat_subg& base, const dcor_hrs_segment& g);
+
+// dcor_hrs_sweep_launch: per segment (reps == 0 included) its descriptor, batch geometry and
+// chunk; need: the largest chunk's noise bytes (0: nothing to run), cap: the largest chunk.
+struct HrsSweepSeg {
+  dcor_premat_subg q;
+  int64_t k, m, cr;
+};
+struct HrsSweepPlan {
+  std::vector<HrsSweepSeg> segs;
+  size_t need = 0;
+  int64_t cap = 0;
+};
+int plan_hrs_sweep(const dcor_premat_subg* base, const dcor_panel* panel,
+                   const dcor_hrs_segment* segs, int64_t nseg, HrsSweepPlan& plan);
+
+// dcor_hrs_fused_sweep_launch: qs, every segment's descriptor (the per-segment fallback's);
+// p0, the first kept segment's constants (the sweep-wide ones are read from it); wide, whether the
+// sweep-wide constants are the same in every kept segment; max_km, the largest k m.
+struct HrsFusedSweepPlan {
+  std::vector<dcor_premat_subg> qs;
+  std::vector<HrsSegConst> tab;
+  PrematSubgConst p0;
+  bool wide = true;
+  int64_t max_km = 0, items = 0;
+};
+int plan_hrs_fused_sweep(const dcor_premat_subg* base, const dcor_panel* panel,
+                         const dcor_hrs_segment* segs, int64_t nseg, HrsFusedSweepPlan& plan);
+
+int plan_sign_panel(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs, int64_t nseg,
+                    std::vector<SignSegConst>& tab, int64_t* items);
+
+#pragma GCC visibility pop
+
+// C linkage and exported, as it has been since the table entry was added: the library's dynamic
+// symbols stay what they were.
+extern "C" int plan_sign_table(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs,
+                               int64_t nseg, std::vector<SignPairSegConst>& tab, int64_t* items);
+
+}  // namespace host
+}  // namespace dcor
