@@ -505,6 +505,56 @@ def sign_table(R, p=8, arm="both"):
         print(json.dumps({"config": "ST-check", "records_bit_equal": same}), flush=True)
 
 
+def hrs_table(R, p=8, arm="both"):
+    """HT: the HRS estimators on every column pair of a p-column stand-in table (n = 19,433) with a
+    clip bound per column: the p (p - 1) / 2 pairs x 23 eps x R sweep in one dcor_hrs_table_launch
+    call (HT-table), and the same work -- same table, bounds, eps grid, keys and R -- as one
+    hrs.sweep_segments(mode='fused') call per pair (HT-pairs), the only route before the table
+    entry.  arm: "table", "pairs" or "both" (both: HT-check reports the records bit-equal).  Not in
+    the default list: reach it with --only HT (--only HT-table / HT-pairs for one arm)."""
+    import numpy as np
+    import torch
+    from dcor import hrs, signpanel
+    Z = signpanel.standin_table(19433, p, 0.3)
+    lam = np.array([2.0 + 0.1 * c for c in range(p)])
+    pairs = signpanel.all_pairs(p)
+    ne = len(hrs.EPS_GRID)
+
+    def table():   # corr_matrix_sweep's segments, without its host-side summaries
+        segs = [(a, b, e, 10 + 1000 * (j * ne + idx), 20 + 1000 * (j * ne + idx), 0, R)
+                for j, (a, b) in enumerate(pairs) for idx, e in enumerate(hrs.EPS_GRID, start=1)]
+        return hrs.table_segments(Z, lam, segs).reshape(len(pairs), ne, R, 6)
+
+    def per_pair():   # sweep_segments keys eps index e with 10 + 1000 (e + 1): pair j's grid is shifted
+        cols = [np.ascontiguousarray(Z[:, c]) for c in range(p)]
+        return np.stack([hrs.sweep_segments(cols[a], cols[b], lam[a], lam[b], [None] * (j * ne) + list(hrs.EPS_GRID),
+                                            [(j * ne + e, 0, R) for e in range(ne)], mode="fused")
+                         for j, (a, b) in enumerate(pairs)]).reshape(len(pairs), ne, R, 6)
+
+    total = len(pairs) * ne * R
+    res = {}
+    for name, fn, kernel, note in (
+            ("HT-table", table, "k_hrs_table_prep + k_hrs_table + k_hrs_sweep_fused_epilogue",
+             "host wall time of one call: table upload, one preparation launch over the columns, one streaming "
+             "and one epilogue launch over every (pair, eps) segment, records copied back"),
+            ("HT-pairs", per_pair, "k_hrs_sweep_fused / k_hrs_sweep_fused_l2 + k_hrs_sweep_fused_epilogue",
+             "host wall time of one sweep_segments(mode='fused') call per pair: two uploads, dcor_panel_create, "
+             "a streaming and an epilogue launch over the pair's 23 eps and a D2H wait each")):
+        if arm != "both" and (arm == "table") != (name == "HT-table"):
+            continue
+        fn()    # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res[name] = fn()
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        line(name, n=int(Z.shape[0]), p=p, pairs=len(pairs), replicates=total, seconds=t, reps_per_s=total / t,
+             finite=bool(np.isfinite(res[name]).all()), kernel=kernel, note=note)
+    if len(res) == 2:
+        same = bool(np.array_equal(res["HT-table"].view(np.uint64), res["HT-pairs"].view(np.uint64)))
+        print(json.dumps({"config": "HT-check", "records_bit_equal": same}), flush=True)
+
+
 def subg():
     from dcor.sim import CellSpec, simulate
     cell = CellSpec(n=100_000, rho=0.5, eps1=1.0, eps2=1.0, family="subG", dgp="bounded_factor", seed=5)
@@ -812,6 +862,9 @@ def main():
     if "ST" in which: sign_table(a.hs_R)
     if "ST-table" in which: sign_table(a.hs_R, arm="table")
     if "ST-pairs" in which: sign_table(a.hs_R, arm="pairs")
+    if "HT" in which: hrs_table(a.hs_R)
+    if "HT-table" in which: hrs_table(a.hs_R, arm="table")
+    if "HT-pairs" in which: hrs_table(a.hs_R, arm="pairs")
     if "S" in which: subg()
     if "R1" in which: rstream_c1()
     if "RG" in which: rstream_grid()

@@ -82,15 +82,19 @@ int upload(DevBuf& b, const T* h, size_t count) {
 // One stream-ordered scratch block of `bytes` ("scratch" or "noise": `kind`) for the work
 // `run(buf)` enqueues on `stream`, whose status is returned; freed in stream order on every path
 // after a successful allocation.  Safe under concurrent launches on different streams.
+// counted: whether the block adds to dcor_alloc_count().  The older entries count theirs (their
+// tests pin that); a block of the stream's pool is no device allocation once the pool is warm, so
+// the table entry, whose contract is that a repeated call adds nothing, does not.
 template <class Run>
-static int with_scratch(const char* entry, const char* kind, size_t bytes, void* stream, Run run) {
+static int with_scratch(const char* entry, const char* kind, size_t bytes, void* stream, Run run,
+                        bool counted = true) {
   void* buf = nullptr;
   const hipStream_t st = (hipStream_t)stream;
   if (hipMallocAsync(&buf, bytes, st) != hipSuccess) {
     (void)hipGetLastError();
     return fail(DCOR_ENOMEM, "%s: cannot allocate %zu %s bytes", entry, bytes, kind);
   }
-  count_alloc();
+  if (counted) count_alloc();
   const int e = run(buf);
   (void)hipFreeAsync(buf, st);
   return e;
@@ -100,14 +104,14 @@ static int with_scratch(const char* entry, const char* kind, size_t bytes, void*
 // `launch(buf)` (hipError_t as int).
 template <class T, class Launch>
 static int with_table(const char* entry, size_t bytes, const std::vector<T>& tab, size_t tab_off,
-                      void* stream, Launch launch) {
+                      void* stream, Launch launch, bool counted = true) {
   return with_scratch(entry, "scratch", bytes, stream, [&](void* buf) {
     // from pageable memory: the copy has left `tab` when the call returns
     int rc = (int)hipMemcpyAsync((char*)buf + tab_off, tab.data(), tab.size() * sizeof(T),
                                  hipMemcpyHostToDevice, (hipStream_t)stream);
     if (!rc) rc = launch(buf);
     return rc ? fail(DCOR_EHIP, "%s launch: %s", entry, hipGetErrorString((hipError_t)rc)) : DCOR_OK;
-  });
+  }, counted);
 }
 
 // MASS::mvrnorm factor A = V diag(sqrt(ev)) of the 2x2 covariance (vert-cor.R:389-394).
@@ -1106,6 +1110,37 @@ int dcor_sign_table_launch(const dcor_sign_table_desc* t, const dcor_sign_pair_s
     return launch_sign_table(tab[0].s, t->D, t->p, t->ld, lay.means(buf), lay.cols(buf), lay.tab(buf),
                              (int)tab.size(), items, d_out, stream);
   });
+}
+
+int dcor_hrs_table_launch(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs,
+                          int64_t nseg, dcor_rep_out* d_out, void* stream) {
+  if (!t || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
+    return fail(DCOR_EINVAL, "hrs_table: null argument");
+  if (nseg == 0) return DCOR_OK;   // nothing to run
+  std::vector<HrsPairSegConst> tab;
+  int64_t items = 0, max_km = 0;
+  if (int st = plan_hrs_table(t, segs, nseg, tab, &items, &max_km)) return st;
+  if (items == 0) return DCOR_OK;
+  if (int st = need_device()) return st;
+  // the call-wide constants (n, nd, sqrt_n, crit, mix, hrs) from the first kept segment's reference
+  // call; everything that depends on lam or eps is read from the table
+  PrematSubgConst p;
+  for (int64_t i = 0; i < nseg; ++i) {
+    if (segs[i].reps == 0) continue;
+    const dcor_premat_subg q = hrs_pair_desc(*t, segs[i]);
+    if (int st = premat_subg_const(&q, p)) return st;
+    break;
+  }
+  p.X = p.Y = nullptr;
+  const HrsTableLayout lay(items, (int64_t)tab.size(), t->n, t->p);
+  return with_table("hrs_table", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
+    // from pageable memory, as the table: the copy has left t->lam when the call returns
+    if (int rc = (int)hipMemcpyAsync(lay.lam(buf), t->lam, (size_t)t->p * sizeof(double),
+                                     hipMemcpyHostToDevice, (hipStream_t)stream))
+      return rc;
+    return launch_hrs_table(p, t->D, t->p, t->ld, lay.lam(buf), lay.cols(buf), lay.npad, lay.tab(buf),
+                            (int)tab.size(), items, max_km, buf, d_out, stream);
+  }, false);
 }
 
 int dcor_panel_dict_probe(const double* d_X, const double* d_Y, int64_t n, int* ok) {

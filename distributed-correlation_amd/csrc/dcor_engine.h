@@ -349,6 +349,49 @@ int launch_hrs_fused_sweep(const PrematSubgConst& c, const HrsSegConst* tab, int
 int persistent_grid(const void* kernel, int threads, size_t lds, int64_t items, int64_t* grid,
                     int lds_limit = 0);
 
+// ---- HRS estimators on the column pairs of a shared table (dcor_hrs_table_launch) ----
+// A fused-sweep segment and the two columns it reads: X = column col_x (the sender), Y = column
+// col_y.  With a clip bound per column nothing that depends on lambda is call-wide, and
+// HrsSegConst already holds every constant of make_subg that depends on lambda or eps (bx, by, bs,
+// lr, s_central, sn2x2, crit_sqrt2_s, eps_r, the geometry): the kernels read nothing else of them
+// (the clips l1 / l2 / ls / lo_ are applied by the preparation launch).
+struct HrsPairSegConst : HrsSegConst {
+  int32_t col_x, col_y;
+};
+static_assert(sizeof(HrsPairSegConst) == 168, "the table entry's device table stride");
+// HRS-table scratch: partials (one SubgPartial per replicate of the call) | the segment table |
+// the p clip bounds | the p clipped columns as plain doubles, each zero-padded to npad = n rounded
+// up to 4, so every column starts 32-B aligned.  Every region starts 256-B aligned when the base
+// is.  ok is false when p * npad * 8 bytes (or the total) is not representable.
+struct HrsTableLayout {
+  int64_t npad;
+  size_t tab_off = 0, lam_off = 0, cols_off = 0, bytes = 0;
+  bool ok = false;
+  HrsTableLayout(int64_t items, int64_t nseg, int64_t n, int64_t p) : npad((n + 3) & ~(int64_t)3) {
+    const size_t lim = SIZE_MAX / 2;
+    if (n < 1 || p < 1 || nseg < 0 || items < 0 || (size_t)p > lim / 16 ||
+        (size_t)nseg > lim / (2 * sizeof(HrsPairSegConst)) || (size_t)items > lim / (2 * sizeof(SubgPartial)))
+      return;
+    tab_off = al256((size_t)items * sizeof(SubgPartial));
+    lam_off = tab_off + al256((size_t)nseg * sizeof(HrsPairSegConst));
+    cols_off = lam_off + al256((size_t)p * sizeof(double));
+    const size_t col_bytes = (size_t)npad * sizeof(double);
+    if (cols_off > lim || (size_t)p > (lim - cols_off) / col_bytes) return;
+    bytes = cols_off + (size_t)p * col_bytes;
+    ok = true;
+  }
+  HrsPairSegConst* tab(void* base) const { return (HrsPairSegConst*)((char*)base + tab_off); }
+  double* lam(void* base) const { return (double*)((char*)base + lam_off); }
+  double* cols(void* base) const { return (double*)((char*)base + cols_off); }
+};
+// The preparation launch (one workgroup per column of D: column c clipped at +-lam[c] with
+// k_premat_xy_pack's rclip, stored at pitch npad) and the streaming and epilogue launches over
+// `items` replicates of the nseg >= 1 segments in `tab` (device), as launch_hrs_fused_sweep.
+// c: any segment's PrematSubgConst (n, nd, sqrt_n, crit, mix, hrs are call-wide); lam: device, [p].
+int launch_hrs_table(const PrematSubgConst& c, const double* D, int64_t p, int64_t ld, const double* lam,
+                     double* cols, int64_t npad, const HrsPairSegConst* tab, int nseg, int64_t items,
+                     int64_t max_km, void* part, dcor_rep_out* out, void* stream);
+
 // ---- sign family on a shared panel (dcor_sign_panel_launch; dcor_signpanel.hip) ----
 // One segment of a sign-panel call: make_sign's constants for the segment's (eps1, eps2) with its
 // Philox key in s.k0 / s.k1 and its first replicate in s.rep_begin, and its place in the call.

@@ -1,6 +1,6 @@
 // dcor_plan.cpp -- the device-free half of the host side (dcor_plan.h): the error reporter, the
 // argument checks of the reference's stopifnot() calls, every data-independent scalar of the
-// estimators (R operation order, cited), and the segment planners of the four segment-list
+// estimators (R operation order, cited), and the segment planners of the five segment-list
 // entries.  No HIP: this file and the headers it includes compile with a host compiler alone.
 #include "dcor_plan.h"
 
@@ -217,17 +217,25 @@ int64_t hrs_chunk(size_t per, int64_t reps, size_t budget, int64_t cap) {
 // ------------------------------------------------------------------ segment planners
 namespace {
 
-// What the three segment types differ in: the name(s) of eps, and the table's columns.
+// What the four segment types differ in: the name(s) of eps, and the table's columns.
 template <class Seg> bool eps_ok(const Seg& g) { return g.eps1 > 0.0 && g.eps2 > 0.0; }
 bool eps_ok(const dcor_hrs_segment& g) { return g.eps > 0.0; }
+bool eps_ok(const dcor_hrs_pair_segment& g) { return g.eps > 0.0; }
 template <class Seg> const char* eps_names(const Seg&) { return "eps1, eps2"; }
 const char* eps_names(const dcor_hrs_segment&) { return "eps"; }
+const char* eps_names(const dcor_hrs_pair_segment&) { return "eps"; }
 template <class Seg> int check_columns(const char*, const Seg&, int64_t, int64_t) { return DCOR_OK; }
-int check_columns(const char* entry, const dcor_sign_pair_segment& g, int64_t i, int64_t p) {
+template <class Seg> int columns_in_range(const char* entry, const Seg& g, int64_t i, int64_t p) {
   if (g.col_x < 0 || g.col_x >= p || g.col_y < 0 || g.col_y >= p)
     return fail(DCOR_EINVAL, "%s: segment %lld: columns (%d, %d) outside [0, %lld)", entry, (long long)i,
                 (int)g.col_x, (int)g.col_y, (long long)p);
   return DCOR_OK;
+}
+int check_columns(const char* entry, const dcor_sign_pair_segment& g, int64_t i, int64_t p) {
+  return columns_in_range(entry, g, i, p);
+}
+int check_columns(const char* entry, const dcor_hrs_pair_segment& g, int64_t i, int64_t p) {
+  return columns_in_range(entry, g, i, p);
 }
 void set_columns(SignSegConst&, const dcor_sign_segment&) {}
 void set_columns(SignPairSegConst& t, const dcor_sign_pair_segment& g) { t.col_x = g.col_x; t.col_y = g.col_y; }
@@ -285,6 +293,22 @@ int check_hrs_base(const char* entry, const dcor_premat_subg* base, const dcor_p
   if (!base->hrs) return fail(DCOR_EINVAL, "%s: the HRS variant only (hrs = 1)", entry);
   if (!(base->delta > 0.0)) return fail(DCOR_EINVAL, "%s: delta must be positive", entry);
   return DCOR_OK;
+}
+
+// The device-table record of a fused HRS segment from its launch constants pc (make_subg's values,
+// unchanged), its keys and its place in the call.
+template <class Seg>
+void hrs_segment_record(const PrematSubgConst& pc, const Seg& g, int64_t first, HrsSegConst& t) {
+  const SubgConst& a = pc.s;
+  t.k = a.k; t.m = a.m; t.md_pow2 = a.md_pow2;
+  t.md = a.md; t.kd = a.kd; t.inv_md = a.inv_md;
+  t.bx = a.bx; t.by = a.by; t.m_over_k = a.m_over_k; t.sqrt_k = a.sqrt_k;
+  t.lr = a.lr; t.bs = a.bs; t.s_central = a.s_central; t.sn2x2 = a.sn2x2; t.eps_r = a.eps_r;
+  t.crit_sqrt2_s = pc.crit_sqrt2_s;
+  t.ni0 = (uint32_t)g.seed_ni; t.ni1 = (uint32_t)(g.seed_ni >> 32);
+  t.in0 = (uint32_t)g.seed_int; t.in1 = (uint32_t)(g.seed_int >> 32);
+  t.rep_begin = (uint32_t)g.rep_begin;
+  t.first = first; t.out_row = g.out_row;
 }
 
 }  // namespace
@@ -349,15 +373,7 @@ int plan_hrs_fused_sweep(const dcor_premat_subg* base, const dcor_panel* panel,
                 std::memcmp(&a.mix, &b.mix, sizeof(a.mix)) == 0;
     HrsSegConst t;
     std::memset(&t, 0, sizeof(t));
-    t.k = a.k; t.m = a.m; t.md_pow2 = a.md_pow2;
-    t.md = a.md; t.kd = a.kd; t.inv_md = a.inv_md;
-    t.bx = a.bx; t.by = a.by; t.m_over_k = a.m_over_k; t.sqrt_k = a.sqrt_k;
-    t.lr = a.lr; t.bs = a.bs; t.s_central = a.s_central; t.sn2x2 = a.sn2x2; t.eps_r = a.eps_r;
-    t.crit_sqrt2_s = pc.crit_sqrt2_s;
-    t.ni0 = (uint32_t)g.seed_ni; t.ni1 = (uint32_t)(g.seed_ni >> 32);
-    t.in0 = (uint32_t)g.seed_int; t.in1 = (uint32_t)(g.seed_int >> 32);
-    t.rep_begin = (uint32_t)g.rep_begin;
-    t.first = first; t.out_row = g.out_row;
+    hrs_segment_record(pc, g, first, t);
     first += g.reps;
     tab.push_back(t);
     plan.max_km = std::max(plan.max_km, a.k * (int64_t)a.m);
@@ -385,6 +401,72 @@ int plan_sign_table(const dcor_sign_table_desc* t, const dcor_sign_pair_segment*
   if (!SignTableLayout((int64_t)tab.size(), t->n, t->p).ok)
     return fail(DCOR_EINVAL, "sign_table: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)",
                 (long long)t->p, (long long)t->n);
+  return DCOR_OK;
+}
+
+dcor_premat_subg hrs_pair_desc(const dcor_hrs_table_desc& t, const dcor_hrs_pair_segment& g) {
+  dcor_premat_subg q;
+  std::memset(&q, 0, sizeof(q));
+  q.n = t.n; q.reps = g.reps;
+  q.eps1 = q.eps2 = g.eps;
+  q.eta1 = q.eta2 = 1.0;
+  q.alpha = t.alpha; q.hrs = 1;
+  q.lam_x = q.lam_s = t.lam[g.col_x];
+  q.lam_y = q.lam_o = t.lam[g.col_y];
+  q.delta = t.delta;
+  q.lam_r = dcor_lambda_receiver_from_noise(q.lam_s, q.lam_o, g.eps, t.delta);
+  q.nsim = t.nsim;
+  q.X = (const double*)((uintptr_t)t.D + (uintptr_t)g.col_x * (uintptr_t)t.ld * sizeof(double));
+  q.Y = (const double*)((uintptr_t)t.D + (uintptr_t)g.col_y * (uintptr_t)t.ld * sizeof(double));
+  return q;
+}
+
+int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs, int64_t nseg,
+                   std::vector<HrsPairSegConst>& tab, int64_t* items, int64_t* max_km) {
+  *items = 0; *max_km = 0;
+  if (!t->D || !t->lam) return fail(DCOR_EINVAL, "hrs_table: null argument (D, lam)");
+  if (t->n < 2 || t->n > DCOR_DICT_NMAX)
+    return fail(DCOR_EINVAL, "hrs_table: n must be in [2, %d] (got %lld): the kernel keeps a replicate's "
+                "u16 batch indices in LDS and there is no fallback for a larger table", DCOR_DICT_NMAX,
+                (long long)t->n);
+  if (t->p < 1 || t->p > 0x7fffffffLL)
+    return fail(DCOR_EINVAL, "hrs_table: p must be in [1, 2^31) (got %lld)", (long long)t->p);
+  if (t->ld < t->n)
+    return fail(DCOR_EINVAL, "hrs_table: ld = %lld < n = %lld", (long long)t->ld, (long long)t->n);
+  if (!HrsTableLayout(0, 0, t->n, t->p).ok)
+    return fail(DCOR_EINVAL, "hrs_table: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)",
+                (long long)t->p, (long long)t->n);
+  if ((uintptr_t)t->D & 7) return fail(DCOR_EINVAL, "hrs_table: D must be aligned to 8 bytes");
+  for (int64_t c = 0; c < t->p; ++c)
+    if (!std::isfinite(t->lam[c]) || !(t->lam[c] > 0.0))
+      return fail(DCOR_EINVAL, "hrs_table: column %lld: lam must be finite and > 0 (got %g)", (long long)c,
+                  t->lam[c]);
+  if (!(t->delta > 0.0)) return fail(DCOR_EINVAL, "hrs_table: delta must be positive");
+  {  // alpha and nsim, as every segment's make_subg would refuse them
+    MixConst mx;
+    if (int st = check_common(t->n, 1.0, 1.0, t->alpha)) return st;
+    if (int st = make_mix(t->nsim, t->alpha, mx)) return st;
+  }
+  if (int st = segment_heads("hrs_table", segs, nseg, t->p, items)) return st;
+  // every segment's launch constants: those of the reference call on its pair, lam and eps
+  int64_t first = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_hrs_pair_segment& g = segs[i];
+    const dcor_premat_subg q = hrs_pair_desc(*t, g);
+    PrematSubgConst pc;
+    if (int st = premat_subg_const(&q, pc)) return st;
+    if (g.reps == 0) continue;
+    HrsPairSegConst r;
+    std::memset(&r, 0, sizeof(r));
+    hrs_segment_record(pc, g, first, r);
+    r.col_x = g.col_x; r.col_y = g.col_y;
+    first += g.reps;
+    tab.push_back(r);
+    *max_km = std::max(*max_km, pc.s.k * (int64_t)pc.s.m);
+  }
+  if (!HrsTableLayout(*items, (int64_t)tab.size(), t->n, t->p).ok)
+    return fail(DCOR_EINVAL, "hrs_table: scratch bytes overflow (p = %lld, n = %lld)", (long long)t->p,
+                (long long)t->n);
   return DCOR_OK;
 }
 

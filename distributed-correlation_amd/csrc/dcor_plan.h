@@ -1,5 +1,5 @@
 // dcor_plan.h -- the host decisions that need no device: the error reporter, the argument checks,
-// every launch constant (R operation order, cited) and the segment planners of the four
+// every launch constant (R operation order, cited) and the segment planners of the five
 // segment-list entries.  Plain C++: neither this header nor dcor_plan.cpp includes the HIP
 // runtime, so the unit compiles, runs and is sanitized with a host compiler alone
 // (tests/host/plan_check.cpp).  Not part of the ABI.
@@ -106,6 +106,19 @@ int plan_hrs_fused_sweep(const dcor_premat_subg* base, const dcor_panel* panel,
 
 int plan_sign_panel(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs, int64_t nseg,
                     std::vector<SignSegConst>& tab, int64_t* items);
+
+// dcor_hrs_table_launch.  The reference call of a segment (include/dcor.h): the descriptor
+// dcor_hrs_fused_launch takes for the pair's columns, clip bounds and eps (lam_x = lam_s =
+// lam[col_x], lam_y = lam_o = lam[col_y], eta = 1, lam_r = lambda_receiver_from_noise; X, Y the
+// columns' addresses, never read here).  g's columns must be in [0, t.p).
+dcor_premat_subg hrs_pair_desc(const dcor_hrs_table_desc& t, const dcor_hrs_pair_segment& g);
+// Every check of the entry after its null checks of t, segs and d_out, in the header's order (D and
+// lam, n, p, ld, the columns' scratch, every lam[c], delta, alpha, nsim, then the segments' fields,
+// columns and ranges, the replicate cap, every segment's constants), then the table: a kept
+// segment's record holds, field for field, what plan_hrs_fused_sweep builds for hrs_pair_desc.
+// items: the call's replicates; max_km: the largest k m of the kept segments.
+int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs, int64_t nseg,
+                   std::vector<HrsPairSegConst>& tab, int64_t* items, int64_t* max_km);
 
 #pragma GCC visibility pop
 

@@ -1796,16 +1796,43 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_fused(PrematSubgConst p, H
   }
 }
 
-// One replicate of the uncoded fused kernels (k_hrs_fused_l2, k_hrs_sweep_fused_l2), as
-// hrs_fused_item: gs is the workgroup's LDS index row (k m u16), the clipped panel p.xyc / p.soc
-// is gathered from L2.
+// The clipped samples of the uncoded fused kernels, gathered from L2.  xy(i): sample i's NI clips
+// (clip(X_i, l1), clip(Y_i, l2)); so(i): its INT clips (sender, other); so2(b, v0, v1): so of the
+// samples 2 b and 2 b + 1 of one local-noise block.
+// The packed panel of k_premat_xy_pack: one 16-B gather per sample.
+struct HrsPackedLoad {
+  const double2* __restrict__ xyc;
+  const double2* __restrict__ soc;
+  __device__ __forceinline__ double2 xy(uint32_t i) const { return xyc[i]; }
+  __device__ __forceinline__ double2 so(int64_t i) const { return soc[i]; }
+  __device__ __forceinline__ void so2(int64_t b, double2& v0, double2& v1) const {
+    v0 = soc[2 * b]; v1 = soc[2 * b + 1];
+  }
+};
+// Two columns of a clipped table (k_hrs_table_prep; each 32-B aligned): X = ca is the sender and
+// a column has one clip bound, so xy and so are the same values; two 8-B gathers per sample, and a
+// local-noise block's two samples as one 16-B read per column.
+struct HrsColumnLoad {
+  const double* __restrict__ ca;
+  const double* __restrict__ cb;
+  __device__ __forceinline__ double2 xy(uint32_t i) const { return make_double2(ca[i], cb[i]); }
+  __device__ __forceinline__ double2 so(int64_t i) const { return make_double2(ca[i], cb[i]); }
+  __device__ __forceinline__ void so2(int64_t b, double2& v0, double2& v1) const {
+    const double2 a = reinterpret_cast<const double2*>(ca)[b], y = reinterpret_cast<const double2*>(cb)[b];
+    v0 = make_double2(a.x, y.x); v1 = make_double2(a.y, y.y);
+  }
+};
+
+// One replicate of the uncoded fused kernels (k_hrs_fused_l2, k_hrs_sweep_fused_l2, k_hrs_table),
+// as hrs_fused_item: gs is the workgroup's LDS index row (k m u16), the clipped samples come from
+// `ld` (above).  The sums' order, the work split, the two phases and the m == 2 path do not depend
+// on the loader, so the kernels agree bit for bit on the same clipped values.
+template <class Load>
 __device__ __forceinline__ void hrs_fused_l2_item(const PrematSubgConst& p, const HrsKeys& hk,
-                                                  uint32_t rep, uint16_t* gs, double* red, int par,
-                                                  SubgPartial* __restrict__ dst) {
+                                                  uint32_t rep, const Load& ld, uint16_t* gs,
+                                                  double* red, int par, SubgPartial* __restrict__ dst) {
   const SubgConst& c = p.s;
   const int tid = threadIdx.x;
-  const double2* __restrict__ xy = p.xyc;
-  const double2* __restrict__ so = p.soc;
   const uint32_t n = (uint32_t)c.n;
   DD sP{0, 0}, sT{0, 0}, sT2{0, 0}, sU{0, 0}, sU2{0, 0};
   auto uval = [&](double2 v, double l) {  // real-data-sims.R:222-232
@@ -1838,12 +1865,13 @@ __device__ __forceinline__ void hrs_fused_l2_item(const PrematSubgConst& p, cons
     const int64_t nb = c.n >> 1;
     for (int64_t b = tid; b < nb; b += DICT_NT) {
       const U4 w = draw((uint32_t)b, rep, HRS_SITE_LOCAL, hk.in0, hk.in1);
-      const double2 v0 = so[2 * b], v1 = so[2 * b + 1];
+      double2 v0, v1;
+      ld.so2(b, v0, v1);
       uterm2(uval(v0, unit_laplace(u53(w.w0, w.w1))), uval(v1, unit_laplace(u53(w.w2, w.w3))));
     }
     if ((c.n & 1) && tid == DICT_NT - 1) {
       const U4 w = draw((uint32_t)nb, rep, HRS_SITE_LOCAL, hk.in0, hk.in1);
-      uterm(uval(so[c.n - 1], unit_laplace(u53(w.w0, w.w1))));
+      uterm(uval(ld.so(c.n - 1), unit_laplace(u53(w.w0, w.w1))));
     }
   }
   double* rb = red + (par & 1) * (10 * DICT_NW);
@@ -1876,11 +1904,11 @@ __device__ __forceinline__ void hrs_fused_l2_item(const PrematSubgConst& p, cons
       const uint32_t ab1 = 2 * q + 1 < c.k ? g2[2 * q + 1] : 0u;
       const U4 wx = draw((uint32_t)q, rep, HRS_SITE_NI_X, hk.ni0, hk.ni1);
       const U4 wy = draw((uint32_t)q, rep, HRS_SITE_NI_Y, hk.ni0, hk.ni1);
-      const double2 a0 = xy[ab0 & 0xFFFFu], b0 = xy[ab0 >> 16];
+      const double2 a0 = ld.xy(ab0 & 0xFFFFu), b0 = ld.xy(ab0 >> 16);
       const double xt0 = (a0.x + b0.x) * 0.5 + c.bx * unit_laplace(u53(wx.w0, wx.w1));
       const double yt0 = (a0.y + b0.y) * 0.5 + c.by * unit_laplace(u53(wy.w0, wy.w1));
       if (2 * q + 1 < c.k) {
-        const double2 a1 = xy[ab1 & 0xFFFFu], b1 = xy[ab1 >> 16];
+        const double2 a1 = ld.xy(ab1 & 0xFFFFu), b1 = ld.xy(ab1 >> 16);
         nterm2(xt0, yt0, (a1.x + b1.x) * 0.5 + c.bx * unit_laplace(u53(wx.w2, wx.w3)),
                (a1.y + b1.y) * 0.5 + c.by * unit_laplace(u53(wy.w2, wy.w3)));
       } else {
@@ -1895,7 +1923,7 @@ __device__ __forceinline__ void hrs_fused_l2_item(const PrematSubgConst& p, cons
       const double lyj = unit_laplace((j & 1) ? u53(wy.w2, wy.w3) : u53(wy.w0, wy.w1));
       DD bx{0, 0}, by{0, 0};
       for (int r = 0; r < c.m; ++r) {
-        const double2 v = xy[gs[j * c.m + r]];
+        const double2 v = ld.xy(gs[j * c.m + r]);
         dd_acc(bx, v.x);
         dd_acc(by, v.y);
       }
@@ -1929,7 +1957,7 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_fused_l2(PrematSubgConst p
   double* red = dsm;
   uint16_t* gs = reinterpret_cast<uint16_t*>(dsm + 20 * DICT_NW);
   for (int64_t it = blockIdx.x; it < reps; it += gridDim.x) {
-    hrs_fused_l2_item(p, hk, hk.rep_begin + (uint32_t)it, gs,
+    hrs_fused_l2_item(p, hk, hk.rep_begin + (uint32_t)it, HrsPackedLoad{p.xyc, p.soc}, gs,
                       red, (int)((it - blockIdx.x) / gridDim.x), part + it);
   }
 }
@@ -2008,10 +2036,13 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_fused_epilogue(PrematSubgCon
 // record equals the per-segment launch's bit for bit.  The table is read through the constant
 // address space at workgroup-uniform addresses: scalar loads into SGPRs, once per segment a
 // workgroup enters, never per lane and never inside the replicate's loops.
-typedef const __attribute__((address_space(4))) HrsSegConst* HrsSegTab;
+// The table's record is HrsSegConst (the sweep) or HrsPairSegConst (the table entry, which adds the
+// segment's two columns): one cursor, search and load for both.
+template <class Seg> using HrsSegTab = const __attribute__((address_space(4))) Seg*;
 
 // The last segment whose first item is <= it (`first` is strictly increasing, tab[0].first = 0).
-__device__ __forceinline__ int hrs_seg_find(HrsSegTab tab, int nseg, int64_t it) {
+template <class Seg>
+__device__ __forceinline__ int hrs_seg_find(HrsSegTab<Seg> tab, int nseg, int64_t it) {
   int lo = 0, hi = nseg - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -2021,7 +2052,8 @@ __device__ __forceinline__ int hrs_seg_find(HrsSegTab tab, int nseg, int64_t it)
 }
 
 // Segment s's constants over the sweep-wide ones in p, its keys into hk.
-__device__ __forceinline__ void hrs_seg_load(HrsSegTab tab, int s, PrematSubgConst& p, HrsKeys& hk) {
+template <class Seg>
+__device__ __forceinline__ void hrs_seg_load(HrsSegTab<Seg> tab, int s, PrematSubgConst& p, HrsKeys& hk) {
   SubgConst& c = p.s;
   c.k = tab[s].k; c.m = tab[s].m; c.md_pow2 = tab[s].md_pow2;
   c.md = tab[s].md; c.kd = tab[s].kd; c.inv_md = tab[s].inv_md;
@@ -2033,16 +2065,18 @@ __device__ __forceinline__ void hrs_seg_load(HrsSegTab tab, int s, PrematSubgCon
 }
 
 // A workgroup's items ascend, so it re-reads the table only when an item passes the end of the
-// segment it holds.
+// segment it holds.  seek returns the segment it loaded, or -1 when the held one still covers `it`.
 struct HrsSegCursor {
   int64_t first = 0, end = 0;   // items [first, end) belong to the loaded segment
-  __device__ __forceinline__ void seek(HrsSegTab tab, int nseg, int64_t items, int64_t it,
-                                       PrematSubgConst& p, HrsKeys& hk) {
-    if (it < end) return;
+  template <class Seg>
+  __device__ __forceinline__ int seek(HrsSegTab<Seg> tab, int nseg, int64_t items, int64_t it,
+                                      PrematSubgConst& p, HrsKeys& hk) {
+    if (it < end) return -1;
     const int s = __builtin_amdgcn_readfirstlane(hrs_seg_find(tab, nseg, it));
     hrs_seg_load(tab, s, p, hk);
     first = tab[s].first;
     end = s + 1 < nseg ? tab[s + 1].first : items;
+    return s;
   }
 };
 
@@ -2058,7 +2092,7 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_sweep_fused(PrematSubgCons
                                                                  int64_t scr_stride) {
   extern __shared__ double dsm[];
   const HrsLds L = hrs_fused_setup(p, codes_g, dict_g, dsm);
-  const HrsSegTab tab = (HrsSegTab)tab_g;
+  const HrsSegTab<HrsSegConst> tab = (HrsSegTab<HrsSegConst>)tab_g;
   HrsKeys hk{0, 0, 0, 0, 0, pa, pc};
   HrsSegCursor cur;
   int par = 0;
@@ -2077,32 +2111,91 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_sweep_fused_l2(PrematSubgC
   extern __shared__ double dsm[];
   double* red = dsm;
   uint16_t* gs = reinterpret_cast<uint16_t*>(dsm + 20 * DICT_NW);  // the largest k m of the segments
-  const HrsSegTab tab = (HrsSegTab)tab_g;
+  const HrsSegTab<HrsSegConst> tab = (HrsSegTab<HrsSegConst>)tab_g;
   HrsKeys hk{0, 0, 0, 0, 0, pa, pc};
   HrsSegCursor cur;
   int par = 0;
   for (int64_t it = blockIdx.x; it < items; it += gridDim.x, par ^= 1) {
     cur.seek(tab, nseg, items, it, p, hk);
-    hrs_fused_l2_item(p, hk, hk.rep_begin + (uint32_t)(it - cur.first), gs,
+    hrs_fused_l2_item(p, hk, hk.rep_begin + (uint32_t)(it - cur.first), HrsPackedLoad{p.xyc, p.soc}, gs,
                       red, par, part + it);
   }
 }
 
-// One epilogue launch over all items: block r finds its segment.
+// One epilogue launch over all items: block r finds its segment.  Seg: the table's record.
+template <class Seg>
 __global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_sweep_fused_epilogue(PrematSubgConst p,
-                                                                         const HrsSegConst* __restrict__ tab_g,
+                                                                         const Seg* __restrict__ tab_g,
                                                                          int nseg,
                                                                          const SubgPartial* __restrict__ part,
                                                                          dcor_rep_out* out) {
   __shared__ SelScratch sel;
   __shared__ double bc[2];
-  const HrsSegTab tab = (HrsSegTab)tab_g;
+  const HrsSegTab<Seg> tab = (HrsSegTab<Seg>)tab_g;
   const int64_t r = blockIdx.x;
   HrsKeys hk{0, 0, 0, 0, 0, 0, 0};   // the epilogue draws no permutation: pa, pc unused
   const int s = __builtin_amdgcn_readfirstlane(hrs_seg_find(tab, nseg, r));
   hrs_seg_load(tab, s, p, hk);
   const int64_t j = r - tab[s].first;
   hrs_fused_epilogue_item(p, hk, hk.rep_begin + (uint32_t)j, r, part, out + tab[s].out_row + j, sel, bc);
+}
+
+// ---------------------------------- the HRS estimators on a table's column pairs ---
+// dcor_hrs_table_launch: k_hrs_sweep_fused_l2's shell over segments that name two columns of a
+// shared table.  A column has one clip bound, X is the sender, so the packed panel's xyc and soc
+// are the same values: one table of clipped columns (8 B per sample and column) serves every pair
+// and both estimators.
+
+// One workgroup per column c of D (column c at D + c ld): rclip(D[c ld + i], lam[c]) -- the bits
+// k_premat_xy_pack forms for the column on either side -- to cols + c npad, zeros from n to npad.
+// Two samples per thread and trip: one 16-B store, and one 16-B load where the caller's column
+// starts on a 16-B boundary (ld is the caller's: a column may start at any 8-B offset).
+#define HRS_PREP_NT 256
+__global__ __launch_bounds__(HRS_PREP_NT) void k_hrs_table_prep(const double* __restrict__ D, int64_t ld,
+                                                                int64_t n, int64_t npad,
+                                                                const double* __restrict__ lam,
+                                                                double* __restrict__ cols) {
+  const int64_t c = blockIdx.x;
+  const double* __restrict__ src = D + c * ld;
+  double2* __restrict__ dst = reinterpret_cast<double2*>(cols + c * npad);
+  const double l = lam[c];
+  const bool al16 = ((uintptr_t)src & 15) == 0;
+  for (int64_t j = threadIdx.x; 2 * j < npad; j += HRS_PREP_NT) {
+    const int64_t i = 2 * j;
+    double2 v = make_double2(0.0, 0.0);
+    if (i + 1 < n) {
+      if (al16) v = *reinterpret_cast<const double2*>(src + i);
+      else v = make_double2(src[i], src[i + 1]);
+      v = make_double2(rclip(v.x, l), rclip(v.y, l));
+    } else if (i < n) {
+      v.x = rclip(src[i], l);
+    }
+    dst[j] = v;
+  }
+}
+
+template <int WPE>
+__global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_table(PrematSubgConst p, int pa, int pc,
+                                                           const HrsPairSegConst* __restrict__ tab_g,
+                                                           int nseg, int64_t items,
+                                                           const double* __restrict__ cols, int64_t pitch,
+                                                           SubgPartial* __restrict__ part) {
+  extern __shared__ double dsm[];
+  double* red = dsm;
+  uint16_t* gs = reinterpret_cast<uint16_t*>(dsm + 20 * DICT_NW);  // the largest k m of the segments
+  const HrsSegTab<HrsPairSegConst> tab = (HrsSegTab<HrsPairSegConst>)tab_g;
+  HrsKeys hk{0, 0, 0, 0, 0, pa, pc};
+  HrsSegCursor cur;
+  HrsColumnLoad ld{nullptr, nullptr};   // the pair's columns: no per-pair state but these pointers
+  int par = 0;
+  for (int64_t it = blockIdx.x; it < items; it += gridDim.x, par ^= 1) {
+    const int s = cur.seek(tab, nseg, items, it, p, hk);
+    if (s >= 0) {   // entered a segment: its columns, at a workgroup-uniform address
+      ld.ca = cols + (int64_t)tab[s].col_x * pitch;
+      ld.cb = cols + (int64_t)tab[s].col_y * pitch;
+    }
+    hrs_fused_l2_item(p, hk, hk.rep_begin + (uint32_t)(it - cur.first), ld, gs, red, par, part + it);
+  }
 }
 
 // ============================================================ launchers ===
@@ -2215,7 +2308,30 @@ int launch_hrs_fused_sweep(const PrematSubgConst& c, const HrsSegConst* tab, int
                        (uint16_t*)scr, stride);
     (void)hipFreeAsync(scr, (hipStream_t)stream);
   }
-  hipLaunchKernelGGL(k_hrs_sweep_fused_epilogue, dim3((unsigned)items), dim3(DCOR_BLOCK), 0,
+  hipLaunchKernelGGL(k_hrs_sweep_fused_epilogue<HrsSegConst>, dim3((unsigned)items), dim3(DCOR_BLOCK), 0,
+                     (hipStream_t)stream, c, tab, nseg, (const SubgPartial*)part, out);
+  return (int)hipGetLastError();
+}
+
+int launch_hrs_table(const PrematSubgConst& c, const double* D, int64_t p, int64_t ld, const double* lam,
+                     double* cols, int64_t npad, const HrsPairSegConst* tab, int nseg, int64_t items,
+                     int64_t max_km, void* part, dcor_rep_out* out, void* stream) {
+  if (items <= 0 || nseg <= 0 || p <= 0) return 0;
+  int pa, pc;
+  hrs_feistel_split(c.s.n, &pa, &pc);
+  const int wsel = (int)dcor::variant("DCOR_HRS_WPE").as_int(6, 4, 4);
+  // k_hrs_sweep_fused_l2's threads and LDS: the reduction buffers and a max_km u16 row
+  const size_t lds = (size_t)(20 * DICT_NW) * sizeof(double) + (size_t)((max_km * 2 + 15) / 16) * 16;
+  typedef void (*TableK)(PrematSubgConst, int, int, const HrsPairSegConst*, int, int64_t, const double*,
+                         int64_t, SubgPartial*);
+  const TableK kern = wsel == 4 ? k_hrs_table<4> : k_hrs_table<6>;
+  int64_t grid = 0;
+  if (int e = persistent_grid((const void*)kern, DICT_NT, lds, items, &grid, kLdsDynMax)) return e;
+  hipLaunchKernelGGL(k_hrs_table_prep, dim3((unsigned)p), dim3(HRS_PREP_NT), 0, (hipStream_t)stream, D, ld,
+                     c.s.n, npad, lam, cols);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c, pa, pc, tab,
+                     nseg, items, (const double*)cols, npad, (SubgPartial*)part);
+  hipLaunchKernelGGL(k_hrs_sweep_fused_epilogue<HrsPairSegConst>, dim3((unsigned)items), dim3(DCOR_BLOCK), 0,
                      (hipStream_t)stream, c, tab, nseg, (const SubgPartial*)part, out);
   return (int)hipGetLastError();
 }

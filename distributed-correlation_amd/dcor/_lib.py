@@ -123,6 +123,18 @@ _D = C.POINTER(C.c_double)
 _I64 = C.POINTER(C.c_int64)
 
 
+class HrsTableDesc(C.Structure):
+    """dcor_hrs_table_desc (include/dcor.h): the shared table (p columns of n samples, ld apart), its
+    per-column clip bounds (a HOST array of p doubles) and the call-wide settings."""
+    _fields_ = [("n", C.c_int64), ("p", C.c_int64), ("ld", C.c_int64), ("D", _P), ("lam", _D),
+                ("alpha", C.c_double), ("delta", C.c_double), ("nsim", C.c_int64)]
+
+
+class HrsPairSegment(C.Structure):
+    """dcor_hrs_pair_segment (include/dcor.h): a dcor_hrs_segment and its (X, Y) columns."""
+    _fields_ = HrsSegment._fields_ + [("col_x", C.c_int32), ("col_y", C.c_int32)]
+
+
 class RsDraws(C.Structure):
     """dcor_rs_draws: host buffers of the R-stream mode's materialised draws."""
     _fields_ = [("X", _D), ("Y", _D), ("lap_ni_sc", _D), ("lap_int_sc", _D), ("lap_ni_x", _D),
@@ -183,6 +195,8 @@ SIGNATURES = {
                                          _P, _P]),
     "dcor_sign_table_launch": (C.c_int, [C.POINTER(SignTableDesc), C.POINTER(SignPairSegment), C.c_int64,
                                          _P, _P]),
+    "dcor_hrs_table_launch": (C.c_int, [C.POINTER(HrsTableDesc), C.POINTER(HrsPairSegment), C.c_int64,
+                                        _P, _P]),
     "dcor_batch_geometry": (C.c_int, [C.c_int64, C.c_double, C.c_double, C.c_int, C.c_int, _I64]),
     "dcor_ci_ni_signbatch": (C.c_int, [_D, _D, C.c_int64, C.c_double, C.c_double, C.c_double,
                                        C.c_int, _D, _D, _D, _D]),

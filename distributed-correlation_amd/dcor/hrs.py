@@ -365,3 +365,105 @@ def sweep_summaries(eps_grid, runs) -> dict:
     ni_mean = [summ("NI", 0, i, eps) for i, eps in enumerate(eps_grid)]
     int_mean = [summ("INT", 3, i, eps) for i, eps in enumerate(eps_grid)]
     return {"eps": list(eps_grid), "runs": runs, "ni_mean": ni_mean, "int_mean": int_mean}
+
+
+# ------------------------------------------------ every column pair of a shared table
+def standardize_table(raw, bounds, lap=None, rng=None):
+    """standardize_panel for the p columns of the (n, p) array raw with per-column clip intervals
+    bounds[c] = (lo, hi): dp_sd, standardize_dp and lambda_from_priv per column
+    (real-data-sims.R:273-287), then the rows with any NaN dropped (drop_na, :282).  lap: optional
+    unit Laplace draws, [mean, m2] of column 0, of column 1, ...  Returns {"Z": (n', p) column-major,
+    "lam": [p], "priv": [p] {'mean', 'sd'}}."""
+    from . import api
+    raw = np.asarray(raw, dtype=np.float64)
+    if raw.ndim != 2 or raw.shape[1] < 1 or len(bounds) != raw.shape[1]:
+        raise ValueError("raw must be an (n, p) array and bounds p (lo, hi) pairs")
+    p = raw.shape[1]
+    lap = np.asarray(api.unit_laplace(2 * p, rng) if lap is None else lap, dtype=np.float64)
+    if lap.shape != (2 * p,):
+        raise ValueError("lap must hold 2 p unit Laplace draws")
+    priv, cols = [], []
+    for c, (lo, hi) in enumerate(bounds):
+        col = np.ascontiguousarray(raw[:, c])
+        priv.append(api.dp_sd(col, lo, hi, EPS_MEAN, EPS_M2, lap=lap[2 * c:2 * c + 2]))
+        cols.append(api.standardize_dp(col, priv[c], lo, hi))
+    Z = np.stack(cols, axis=1)
+    ok = ~np.isnan(Z).any(axis=1)
+    lam = np.array([api.lambda_from_priv(lo, hi, pv) for (lo, hi), pv in zip(bounds, priv)], dtype=np.float64)
+    return {"Z": np.asfortranarray(Z[ok]), "lam": lam, "priv": priv}
+
+
+def table_segments(Z, lam, segs, nsim=2000, alpha=0.05, delta=None, stream=None):
+    """The HRS replicates of several (col_x, col_y, eps, seed_ni, seed_int, rep_begin, reps) segments
+    on the columns of one shared (n, p) table of standardised variables, column c clipped at
+    +-lam[c], in one native call (dcor_hrs_table_launch): one upload (a column-major Z is not
+    copied), one preparation launch, every pair and eps in one streaming launch -> float64
+    [sum(reps), 6] in segment order.  Each segment's records equal hrs_replicates(Z[:, col_x],
+    Z[:, col_y], lam[col_x], lam[col_y], eps, reps, seed_ni, seed_int, rep_begin=rep_begin,
+    mode='fused') byte for byte; X (col_x) is the sender, so (a, b) and (b, a) are different
+    segments.  delta: delta_clip, 1 / n by default (real-data-sims.R:199)."""
+    import ctypes as C
+
+    from . import _lib
+    from .signpanel import _table
+    segs = list(segs)
+    F, n, p = _table(Z)
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    if lam.shape != (p,):
+        raise ValueError(f"lam must hold one clip bound per column ({p})")
+    for a, b, *_ in segs:
+        if not (0 <= int(a) < p and 0 <= int(b) < p):
+            raise ValueError(f"columns ({a}, {b}) outside [0, {p})")
+    rows = np.cumsum([0] + [int(s[6]) for s in segs])
+    total = int(rows[-1])
+    arr = (_lib.HrsPairSegment * max(len(segs), 1))(*[
+        _lib.HrsPairSegment(eps=float(e), seed_ni=int(sn), seed_int=int(si), rep_begin=int(rb), reps=int(c),
+                            out_row=int(rows[j]), col_x=int(a), col_y=int(b))
+        for j, (a, b, e, sn, si, rb, c) in enumerate(segs)])
+    import torch
+    Dd = torch.as_tensor(F.reshape(-1, order="F"), device="cuda")   # the one upload
+    st = torch.cuda.current_stream() if stream is None else stream
+    out = torch.empty((max(total, 1), 6), dtype=torch.float64, device="cuda")
+    desc = _lib.HrsTableDesc(n=n, p=p, ld=n, D=Dd.data_ptr(), lam=lam.ctypes.data_as(C.POINTER(C.c_double)),
+                             alpha=float(alpha), delta=1.0 / n if delta is None else float(delta),
+                             nsim=int(nsim))
+    with torch.cuda.stream(st):
+        _lib.check(_lib.lib.dcor_hrs_table_launch(C.byref(desc), arr, len(segs),
+                                                  C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
+        res = out[:total].cpu().numpy()   # waits for the stream: the table outlives the call's work
+    return res
+
+
+def corr_matrix(Z, lam, eps, reps, pairs=None, nsim=2000, alpha=0.05, delta=None, stream=None):
+    """The private correlation of every column pair of the standardised (n, p) table Z under the
+    study's estimators at one eps: `reps` runs per pair in one native call.  pairs: every a < b in
+    row-major order by default; pair j runs under the keys of corr_matrix_sweep with a one-eps grid,
+    10 + 1000 (j + 1) and 20 + 1000 (j + 1).  Returns what dcor.signpanel.corr_matrix returns:
+    {"pairs", "runs" [npairs, reps, 6], "ni", "int"}."""
+    from .signpanel import _pair_matrices, _table, all_pairs
+    _, _, p = _table(Z)
+    pairs = all_pairs(p) if pairs is None else [(int(a), int(b)) for a, b in pairs]
+    segs = [(a, b, eps, 10 + 1000 * (j + 1), 20 + 1000 * (j + 1), 0, reps) for j, (a, b) in enumerate(pairs)]
+    runs = table_segments(Z, lam, segs, nsim=nsim, alpha=alpha, delta=delta,
+                          stream=stream).reshape(len(pairs), reps, 6)
+    return {"pairs": pairs, "runs": runs, **_pair_matrices(p, pairs, runs)}
+
+
+def corr_matrix_sweep(Z, lam, eps_grid=EPS_GRID, reps=R_PER_EPS, pairs=None, nsim=2000, alpha=0.05,
+                      delta=None, stream=None):
+    """The replicate sweep of real-data-sims.R:345-448 for every pair and every eps of eps_grid,
+    pairs x eps in one native call.  Pair j at eps index idx (1-based) runs under Philox keys
+    10 + 1000 (j n_eps + idx) and 20 + 1000 (j n_eps + idx), so pair 0's part equals
+    eps_sweep(mode='fused') on its columns.  Returns what dcor.signpanel.corr_matrix_sweep returns:
+    {"pairs", "eps", "runs" [npairs, n_eps, reps, 6], "summaries"}."""
+    from .signpanel import _table, all_pairs
+    eps_grid = list(eps_grid)
+    _, _, p = _table(Z)
+    pairs = all_pairs(p) if pairs is None else [(int(a), int(b)) for a, b in pairs]
+    ne = len(eps_grid)
+    segs = [(a, b, e, 10 + 1000 * (j * ne + idx), 20 + 1000 * (j * ne + idx), 0, reps)
+            for j, (a, b) in enumerate(pairs) for idx, e in enumerate(eps_grid, start=1)]
+    runs = table_segments(Z, lam, segs, nsim=nsim, alpha=alpha, delta=delta,
+                          stream=stream).reshape(len(pairs), ne, reps, 6)
+    return {"pairs": pairs, "eps": eps_grid, "runs": runs,
+            "summaries": [sweep_summaries(eps_grid, runs[j]) for j in range(len(pairs))]}

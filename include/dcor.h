@@ -467,6 +467,53 @@ typedef struct dcor_sign_pair_segment {
 int dcor_sign_table_launch(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream);
 
+/* The HRS estimators (correlation_NI_subG with lambda overrides and random batches,
+ * real-data-sims.R:115-147; ci_INT_subG with lambda_receiver_from_noise, :176-252) for any column
+ * pairs of one shared table of standardised variables: the table form of
+ * dcor_hrs_fused_sweep_launch, as dcor_sign_table_launch is of dcor_sign_panel_launch.  D holds p
+ * columns of n samples, column c at D + c * ld, and lam[c] is column c's one clip bound
+ * (lambda_from_priv): lambda_X / lambda_Y on the NI side and lambda_sender / lambda_other on the
+ * INT side.  A segment names its pair: X = column col_x (the sender; eps1 = eps2 = eps), Y = column
+ * col_y; (a, b) and (b, a) are different segments and col_x == col_y is allowed.  The records of a
+ * segment equal, byte for byte, the records of dcor_hrs_fused_sweep_launch (equally
+ * dcor_hrs_fused_launch, whichever kernel it picks) on a panel created on X = column col_x, Y =
+ * column col_y with lam_x = lam_s = lam[col_x], lam_y = lam_o = lam[col_y] and the same delta,
+ * alpha, nsim, eps, seeds, rep_begin and reps: the same per-replicate code, the same draw sites
+ * (DCOR_SITE_PERM, 11 / 12 under seed_ni, 13 .. 16 under seed_int), the same HRS geometry (k < 2:
+ * k = 2, m = floor(n / 2)).  A NaN in a column reaches only the pairs that name it.  Records depend
+ * only on (columns, lam, eps, seeds, replicate), never on the segment split or the order of
+ * segments.  One preparation launch (one workgroup per column: the column clipped at +-lam[c], the
+ * bits k_premat_xy_pack forms for it on either side) and one streaming launch plus one epilogue
+ * launch cover every pair and every eps; a segment's constants, all of which depend on its
+ * columns' lam or its eps, come from a device table.
+ * Checks, all before anything is enqueued and before any device access (an invalid call returns
+ * its code and leaves d_out untouched): non-null t, D, lam, segs, d_out; 2 <= n <= 65536 (the
+ * kernel keeps a replicate's u16 batch indices in LDS: a larger n is DCOR_EINVAL, there is no
+ * fallback); 1 <= p < 2^31, ld >= n, p * npad * 8 scratch bytes representable (npad: n rounded up
+ * to a multiple of 4); every lam[c] finite and > 0 (dcor_last_error names the column); delta > 0;
+ * alpha, nsim as dcor_hrs_fused_sweep_launch; per segment eps > 0, reps, rep_begin, out_row >= 0,
+ * rep_begin + reps <= 2^32, 0 <= col_x, col_y < p (dcor_last_error names the segment); at most
+ * 2^31 - 1 replicates per call.  nseg == 0 or no replicates at all returns DCOR_OK with no device
+ * work.  Asynchronous on `stream`, no host synchronisation; scratch is stream-ordered (8 B per
+ * sample and column, 8 B per column, the segment table, 80 B per replicate) -- no noise array, no
+ * dcor_panel.  DCOR_HRS_WPE acts as in dcor_hrs_fused_launch.  D, lam and segs are borrowed for
+ * the call only (D until the call's work on `stream` has run). */
+typedef struct dcor_hrs_table_desc {
+  int64_t n, p, ld;         /* samples per column, columns, elements between column starts */
+  const double* D;          /* DEVICE, column c = D + c * ld; borrowed for the call */
+  const double* lam;        /* HOST, [p]: column c's clip bound, finite and > 0 */
+  double alpha, delta;      /* delta > 0: delta_clip (the Python layer passes 1/n) */
+  int64_t nsim;
+} dcor_hrs_table_desc;
+typedef struct dcor_hrs_pair_segment {
+  double eps;
+  uint64_t seed_ni, seed_int;
+  int64_t rep_begin, reps, out_row;
+  int32_t col_x, col_y;     /* X = column col_x (the sender), Y = column col_y */
+} dcor_hrs_pair_segment;
+int dcor_hrs_table_launch(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs,
+                          int64_t nseg, dcor_rep_out* d_out, void* stream);
+
 int dcor_premat_sign_launch(const dcor_premat_sign* d, dcor_rep_out* d_out, void* stream);
 int dcor_premat_subg_launch(const dcor_premat_subg* d, dcor_rep_out* d_out, void* stream);
 
