@@ -814,14 +814,20 @@ __device__ __forceinline__ P2Result sign_pass2_core(const SignConst& c, uint32_t
   // Two records (one word) by SWAR: g = w | 0x80 per byte, g - T per byte has bit 7 = (q >= t) with
   // no borrow between bytes (0x80 + q - t >= 1), and g - (T + 1) has it = (q > t): the two differ
   // exactly on a tie.  neg counts (q < t) per byte (x0, y0, x1, y1); the INT bit of each record is
-  // px ^ py ^ S (bits 7, 23 of dI ^ dI >> 8 ^ w), +1 when set.  13 full-rate operations and one
-  // v_bcnt for two records.
+  // px ^ py ^ S (bits 7, 23 of dI ^ dI >> 8 ^ w), +1 when set.  The three-input bit operations are
+  // v_bitop3_b32 by the builtin (the compiler forms none by itself, dcor_device.h); its truth table
+  // is the expression evaluated on a = 0xF0, b = 0xCC, c = 0xAA.  13 full-rate operations, 4 of them
+  // bitop3, and one v_bcnt (adding through its addend) for two records.
   auto word2 = [&](uint32_t w, uint32_t& neg, uint32_t& pc, uint32_t& tie) {
     const uint32_t g = w | 0x80808080u;
     const uint32_t dN = g - TN4, dN1 = g - TN4p, dI = g - TI4, dI1 = g - TI4p;
-    tie |= (dN ^ dN1) | (dI ^ dI1);
-    neg += (~dN >> 7) & 0x01010101u;
-    pc += (uint32_t)__popc((dI ^ (dI >> 8) ^ w) & 0x00800080u);
+    // tie |= (dN ^ dN1) | (dI ^ dI1), twice a | (b ^ c): 0xF0 | (0xCC ^ 0xAA) = 0xF6
+    tie = __builtin_amdgcn_bitop3_b32(tie, dN, dN1, 0xF6);
+    tie = __builtin_amdgcn_bitop3_b32(tie, dI, dI1, 0xF6);
+    // (~dN >> 7) & 0x01010101 as ~(dN >> 7) & mask (the mask has no bit the shift fills), ~a & b:
+    // ~0xF0 & 0xCC = 0x0C
+    neg += __builtin_amdgcn_bitop3_b32(dN >> 7, 0x01010101u, 0u, 0x0C);
+    pc += (uint32_t)__popc(xor3(dI, dI >> 8, w) & 0x00800080u);
   };
   // mean of m signs = count / m (exact quotient for the configs' m); a power-of-two m divides by
   // an exact multiply.  M8: the headline geometry, m = 8 known at compile time.
@@ -842,11 +848,16 @@ __device__ __forceinline__ P2Result sign_pass2_core(const SignConst& c, uint32_t
     ks_acc(sT, T);  // compensated (error ~ k 2^-106): the T mean / sd inputs
     ks_acc(sT2, T * T);
   };
-  // T_j alone (no accumulation): the pair-grouped form below
-  auto batch_T_val = [&](int64_t j, int cx, int cy) -> double {
-    const U4 w = draw((uint32_t)j, rep, DCOR_SITE_NI_LAP, c.k0, c.k1);   // vert-cor.R:230-231
-    const double xt = (double)cx * 0.125 + c.bx * unit_laplace_t(u53(w.w0, w.w1), lt);
-    const double yt = (double)cy * 0.125 + c.by * unit_laplace_t(u53(w.w2, w.w3), lt);
+  // T_j alone (no accumulation): the pair-grouped form below.  The m = 8 instantiation holds the
+  // two noise scales in vector registers: its loop is short of scalar ones (the Philox round keys
+  // alone take 19), and the allocator otherwise parks these two in lanes and reads them back every
+  // trip.  (Not the generic instantiations: k_sign_p2e_w has no vector register to spare.)
+  double bxv = c.bx, byv = c.by;
+  if constexpr (ONLY8) asm volatile("" : "+v"(bxv), "+v"(byv));
+  auto batch_T_val = [&](uint32_t j, int cx, int cy) -> double {
+    const U4 w = draw(j, rep, DCOR_SITE_NI_LAP, c.k0, c.k1);             // vert-cor.R:230-231
+    const double xt = (double)cx * 0.125 + bxv * unit_laplace_t(u53(w.w0, w.w1), lt);
+    const double yt = (double)cy * 0.125 + byv * unit_laplace_t(u53(w.w2, w.w3), lt);
     return 8.0 * xt * yt;                                                 // vert-cor.R:233
   };
   // Tie deferral.  A batch whose codes tie a threshold (about 1e-3 of records at the headline's 128
@@ -916,8 +927,11 @@ __device__ __forceinline__ P2Result sign_pass2_core(const SignConst& c, uint32_t
   };
   if (ONLY8 || c.m == 8) {
     // headline geometry: one thread = one batch = one 16-B load (8 records), decided by word2.
-    auto decide = [&](const uint4& v, int& cx, int& cy, int& cc) -> bool {
-      uint32_t neg = 0, pc = 0, tie = 0;
+    // Returns the batch's tie word: bit 7 of a byte set when a code ties a threshold's -- and in
+    // every batch of a replicate that is decided exactly (force_exact), by the word's first value.
+    const uint32_t tie0 = force_exact ? 0x80u : 0u;
+    auto decide = [&](const uint4& v, int& cx, int& cy, int& cc) -> uint32_t {
+      uint32_t neg = 0, pc = 0, tie = tie0;
       word2(v.x, neg, pc, tie);
       word2(v.y, neg, pc, tie);
       word2(v.z, neg, pc, tie);
@@ -929,56 +943,72 @@ __device__ __forceinline__ P2Result sign_pass2_core(const SignConst& c, uint32_t
       if constexpr (CEIL) {
         asm volatile("" : "+v"(tie));
         cc += (int)(tie & 1u);
-        return false;
+        return 0u;
       }
-      return (tie & 0x80808080u) != 0 || force_exact;
+      return tie & 0x80808080u;
     };
     // Two batches in flight per thread in two register sets, used in place (a move of a register
     // with a load pending waits for the load): batch j is decided while j + NT loads, j + 2 NT is
-    // issued into j's registers, then j + NT is decided.  The trip count is uniform per wave; loads
-    // past the last batch re-read it, and batches past it are dropped.
-    auto load = [&](int64_t jj, uint4& v) {
-      if constexpr (CEIL) {
+    // issued into j's registers, then j + NT is decided.  The trip count is uniform per wave.
+    // Batch indices are 32-bit: n < 2^31 (check_common), so k = n / 8 < 2^28, a batch's byte
+    // offset 16 j is below 2^32 and every index formed here (at most k + 3 NT) fits; the slab base
+    // is the one 64-bit value.
+    const uint32_t k32 = (uint32_t)c.k;
+    const char* slab8 = reinterpret_cast<const char*>(slab);
+    auto ld = [&](uint32_t jj) { return *reinterpret_cast<const uint4*>(slab8 + 16u * jj); };   // jj < k32
+    // TAIL: loads past the last batch re-read it
+    auto load = [&](uint32_t jj, uint4& v, auto tail_tag) {
+      if constexpr (CEIL)
         asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
-      } else {
-        const int64_t jc = jj < c.k ? jj : c.k - 1;
-        v = slab_ld4(slab + 4 * jc);
-      }
+      else if constexpr (decltype(tail_tag)::value)
+        v = ld(jj < k32 ? jj : k32 - 1u);
+      else
+        v = ld(jj);
     };
-    if (c.k > 0) {
-      const int64_t base = tid - lane;       // the wave's first batch
+    if (k32 > 0) {
       uint4 a, b;
-      {
-        const int64_t ja = tid < c.k ? tid : c.k - 1, jb = tid + NT < c.k ? tid + NT : c.k - 1;
-        a = slab_ld4(slab + 4 * ja);
-        __builtin_amdgcn_sched_barrier(0);
-        b = slab_ld4(slab + 4 * jb);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      for (int64_t jw = base; jw < c.k; jw += 2 * NT) {   // uniform per wave
-        const int64_t j = jw + lane, jb = j + NT;
-        const bool va = j < c.k, vb = jb < c.k;
+      a = ld((uint32_t)tid < k32 ? (uint32_t)tid : k32 - 1u);
+      __builtin_amdgcn_sched_barrier(0);
+      b = ld((uint32_t)tid + NT < k32 ? (uint32_t)tid + NT : k32 - 1u);
+      __builtin_amdgcn_sched_barrier(0);
+      // One trip: the thread's batches j and j + NT.  TAIL = false is the steady state, every lane's
+      // two batches and its two prefetched ones in range: no clamp, no validity flag, no select.
+      // A batch that ties is deferred, one that is past the end (TAIL) is dropped; either adds 0 to
+      // the sums.  All of that sits behind one wave-uniform test, which a trip of whole batches
+      // without a tie (nearly every one: the headline has 0.4 tie batches per replicate) fails.
+      // The queue count changes only in such a trip, so drain_if_full is asked only after one.
+      auto trip = [&](uint32_t j, auto tail_tag) {
+        constexpr bool TAIL = decltype(tail_tag)::value;
+        const uint32_t jb = j + NT;
         int cxa, cya, cca, cxb, cyb, ccb;
-        const bool ta = decide(a, cxa, cya, cca);
-        load(j + 2 * NT, a);
+        const uint32_t ua = decide(a, cxa, cya, cca);
+        load(j + 2 * NT, a, tail_tag);
         __builtin_amdgcn_sched_barrier(0);  // keep j + NT's decisions after j + 2 NT's loads
-        const bool tb = decide(b, cxb, cyb, ccb);
-        load(j + 3 * NT, b);
+        const uint32_t ub = decide(b, cxb, cyb, ccb);
+        load(j + 3 * NT, b, tail_tag);
         __builtin_amdgcn_sched_barrier(0);
-        // defer() is called by every lane (its ballot and the queue count are wave-wide)
-        const bool fa = defer(va && ta, j);
-        const bool fb = defer(vb && tb, jb);
-        const bool da = va && !fa, db = vb && !fb;
-        core += (da ? cca : 0) + (db ? ccb : 0);
+        const bool xa = TAIL && j >= k32, xb = TAIL && jb >= k32;   // past the end
         // the two batches' T and T^2 added plainly, the pair sums compensated: half the TwoSum
-        // chains (the low bits differ from per-batch sums, within the oracle's 1e-12); a batch
-        // dropped here (past the end or deferred) adds 0
-        const double Ta = da ? batch_T_val(j, cxa, cya) : 0.0;
-        const double Tb = db ? batch_T_val(jb, cxb, cyb) : 0.0;
+        // chains (the low bits differ from per-batch sums, within the oracle's 1e-12)
+        double Ta = batch_T_val(j, cxa, cya), Tb = batch_T_val(jb, cxb, cyb);
+        const bool rare = __builtin_amdgcn_ballot_w64((ua | ub) != 0 || xa || xb) != 0;
+        if (__builtin_expect(rare, 0)) {
+          // defer() is called by every lane (its ballot and the queue count are wave-wide)
+          const bool ta = ua != 0 && !xa, tb = ub != 0 && !xb;
+          defer(ta, j);
+          defer(tb, jb);
+          if (ta || xa) { cca = 0; Ta = 0.0; }
+          if (tb || xb) { ccb = 0; Tb = 0.0; }
+        }
+        core += cca + ccb;
         ks_acc(sT, Ta + Tb);
         ks_acc(sT2, Ta * Ta + Tb * Tb);
-        drain_if_full(128u);
-      }
+        if (__builtin_expect(rare, 0)) drain_if_full(128u);   // after the trip's own sums: the drain adds to them
+      };
+      // the wave's first batch (uniform), then its steady trips, then the guarded ones (at most two)
+      uint32_t jw = WAVE ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane(tid - lane);
+      for (; jw + (3 * NT + 64) <= k32; jw += 2 * NT) trip(jw + (uint32_t)lane, std::false_type());
+      for (; jw < k32; jw += 2 * NT) trip(jw + (uint32_t)lane, std::true_type());
     }
   } else if constexpr (!CEIL && !ONLY8) {
     // m % 8 == 0, 16 <= m <= 248 (the grids' 32, C4's 200): 16-B pieces of 8 records.  A replicate's
