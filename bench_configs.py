@@ -456,6 +456,69 @@ def sign_panel(R, big=100_000):
                   "over every segment, records copied back")
 
 
+def subg_panel(R, arm="all", big=8192, n_big=100_000, chunk=1024):
+    """SGP: the simulation's sub-G estimators on a shared panel with every draw made inside the
+    kernel (dcor_subg_panel_launch): `big` replicates at eps = (1, 1) on the two columns of
+    signpanel.standin_table(n_big, 2, 0.3).  SGP-sweep: the 23 eps x R sweep at n = 19,433 in one
+    call.  SGP-premat: SGP's work by the route that existed before the entry -- Philox noise
+    materialised in HBM with dcor_draws_launch in chunks of `chunk` replicates (lap_local alone is n
+    doubles per replicate) and run through dcor_premat_subg_launch with hrs = 0 on the shared panel
+    (xy_stride = 0).  arm: "panel", "sweep", "premat" or "all".  Not in the default list: reach it
+    with --only SGP (--only SGP-panel / SGP-sweep / SGP-premat for one arm)."""
+    import ctypes as C
+
+    import numpy as np
+    import torch
+    from dcor import _lib, hrs, signpanel, subgpanel
+    D = signpanel.standin_table(n_big, 2, 0.3)
+    X, Y = np.ascontiguousarray(D[:, 0]), np.ascontiguousarray(D[:, 1])
+    D2 = signpanel.standin_table(19433, 2, 0.3)
+    X2, Y2 = np.ascontiguousarray(D2[:, 0]), np.ascontiguousarray(D2[:, 1])
+
+    def premat():
+        n, nsim, k = n_big, 1000, n_big // 8
+        st = torch.cuda.current_stream()
+        sp = C.c_void_p(st.cuda_stream)
+        Xd, Yd = torch.as_tensor(X, device="cuda"), torch.as_tensor(Y, device="cuda")
+        out = torch.empty((big, 6), dtype=torch.float64, device="cuda")
+        cr = min(chunk, big)
+        bufs = {name: torch.empty((cr, cnt), dtype=torch.float64, device="cuda")
+                for name, cnt in (("lap_ni_x", k), ("lap_ni_y", k), ("lap_local", n), ("lap_central", 1),
+                                  ("mix_z", nsim), ("mix_l", nsim))}
+        sites = {"lap_ni_x": (0, 11), "lap_ni_y": (0, 12), "lap_local": (0, 13), "lap_central": (0, 14),
+                 "mix_z": (1, 15), "mix_l": (0, 16)}
+        nan = float("nan")
+        for r0 in range(0, big, cr):
+            c = min(cr, big - r0)
+            for name, (kind, site) in sites.items():
+                _lib.check(_lib.lib.dcor_draws_launch(kind, 1_000_001, site, r0, c, bufs[name].shape[1],
+                                                      C.c_void_p(bufs[name].data_ptr()), sp))
+            d = _lib.PrematSubg(n=n, reps=c, eps1=1.0, eps2=1.0, eta1=1.0, eta2=1.0, alpha=0.05, hrs=0,
+                                lam_x=nan, lam_y=nan, lam_s=nan, lam_o=nan, lam_r=nan, delta=nan, nsim=nsim,
+                                X=Xd.data_ptr(), Y=Yd.data_ptr(), xy_stride=0, perm=None,
+                                **{name: b.data_ptr() for name, b in bufs.items()})
+            _lib.check(_lib.lib.dcor_premat_subg_launch(C.byref(d), C.c_void_p(out[r0:].data_ptr()), sp))
+        return out.cpu().numpy()
+
+    arms = (("SGP", "panel", lambda: subgpanel.replicates(X, Y, 1.0, 1.0, big, seed=1_000_001), big, n_big,
+             "k_subg_panel_prep + k_subg_panel"),
+            ("SGP-sweep", "sweep", lambda: subgpanel.eps_sweep(X2, Y2, hrs.EPS_GRID, R)["runs"],
+             len(hrs.EPS_GRID) * R, 19433, "k_subg_panel_prep + k_subg_panel"),
+            ("SGP-premat", "premat", premat, big, n_big, "k_draws x 6 + k_premat_subg_stream + epilogue per chunk"))
+    for name, key, fn, total, n, kernel in arms:
+        if arm not in ("all", key):
+            continue
+        fn()    # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = fn()
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        line(name, n=n, replicates=total, seconds=t, reps_per_s=total / t,
+             finite=bool(np.isfinite(res).all()), kernel=kernel,
+             note="host wall time of one call: panel upload, the launches, records copied back")
+
+
 def sign_table(R, p=8, arm="both"):
     """ST: the sign family on every column pair of a p-column stand-in table (n = 19,433): the
     p (p - 1) / 2 pairs x 23 eps x R sweep in one dcor_sign_table_launch call (ST), and the same
@@ -859,6 +922,10 @@ def main():
     if "HS" in which: hrs_sweep(a.hs_R)
     if "HSf" in which: hrs_sweep_fused(a.hs_R)
     if "SP" in which: sign_panel(a.hs_R)
+    if "SGP" in which: subg_panel(a.hs_R)
+    if "SGP-panel" in which: subg_panel(a.hs_R, arm="panel")
+    if "SGP-sweep" in which: subg_panel(a.hs_R, arm="sweep")
+    if "SGP-premat" in which: subg_panel(a.hs_R, arm="premat")
     if "ST" in which: sign_table(a.hs_R)
     if "ST-table" in which: sign_table(a.hs_R, arm="table")
     if "ST-pairs" in which: sign_table(a.hs_R, arm="pairs")

@@ -1143,6 +1143,30 @@ int dcor_hrs_table_launch(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segm
   }, false);
 }
 
+int dcor_subg_panel_launch(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs,
+                           int64_t nseg, dcor_rep_out* d_out, void* stream) {
+  if (!p || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
+    return fail(DCOR_EINVAL, "subg_panel: null argument");
+  if (nseg == 0) return DCOR_OK;   // nothing to run
+  std::vector<SubgSegConst> tab;
+  std::vector<SubgMeanSlot> slots;
+  SubgConst c0;
+  int64_t items = 0;
+  if (int st = plan_subg_panel(p, segs, nseg, tab, slots, &c0, &items)) return st;
+  if (items == 0) return DCOR_OK;
+  if (int st = need_device()) return st;
+  const int64_t nmeans = slots.back().off + slots.back().k;
+  const SubgPanelLayout lay((int64_t)tab.size(), (int64_t)slots.size(), nmeans, p->n);
+  return with_table("subg_panel", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
+    // from pageable memory, as the table: the copy has left `slots` when the call returns
+    if (int rc = (int)hipMemcpyAsync(lay.slots(buf), slots.data(), slots.size() * sizeof(SubgMeanSlot),
+                                     hipMemcpyHostToDevice, (hipStream_t)stream))
+      return rc;
+    return launch_subg_panel(c0, p->X, p->Y, lay.slots(buf), (int)slots.size(), lay.means(buf), lay.xy(buf),
+                             lay.npad, lay.tab(buf), (int)tab.size(), items, d_out, stream);
+  }, false);
+}
+
 int dcor_panel_dict_probe(const double* d_X, const double* d_Y, int64_t n, int* ok) {
   if (!d_X || !d_Y || !ok || n < 1) return fail(DCOR_EINVAL, "panel_dict_probe: bad arguments");
   if (int st = need_device()) return st;

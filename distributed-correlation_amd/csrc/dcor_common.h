@@ -215,5 +215,59 @@ __device__ __forceinline__ void ni_subg_result(const SubgConst& c, DD sP, DD sT,
   o[2] = rmin(rho + c.crit * se, 1.0);
 }
 
+// Wave-level mixquant from Philox (one replicate per wave): the same elements as
+// mixquant_fused, VPL keys per lane, written to the wave's LDS and selected there.
+template <int VPL>
+struct WaveMix {
+  double keys[64 * VPL];
+  WaveSelL sel;
+};
+
+template <int VPL>
+__device__ __forceinline__ double wave_mixquant_fused(const MixConst& mx, double c, uint32_t rep,
+                                                      uint32_t k0, uint32_t k1, WaveMix<VPL>* ws) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int s = 0; s < VPL / 2; ++s) {
+    const int b = lane + 64 * s;  // Philox block b -> elements 2b, 2b+1
+    double v0 = dnan(), v1 = dnan();
+    if (2 * b < mx.nsim) {
+      const U4 wz = draw((uint32_t)b, rep, DCOR_SITE_MIX_Z, k0, k1);
+      const U4 wl = draw((uint32_t)b, rep, DCOR_SITE_MIX_L, k0, k1);
+      double z0, z1;
+      normal_pair(wz, &z0, &z1);
+      v0 = z0 + c * unit_laplace(u53(wl.w0, wl.w1));
+      if (2 * b + 1 < mx.nsim) v1 = z1 + c * unit_laplace(u53(wl.w2, wl.w3));
+    }
+    ws->keys[lane + 64 * (2 * s)] = v0;
+    ws->keys[lane + 64 * (2 * s + 1)] = v1;
+  }
+  wave_sync();
+  return wave_select_lds<VPL>(ws->keys, mx.pos, &ws->sel);
+}
+
+// The INT tail of a sub-G replicate (ver-cor-subG.R:91-103) from the sums of Uc and Uc^2 over all
+// n samples and the central unit Laplace lapz: o[3..5] = the estimate and its CI.  The tail of the
+// fused engine's subg_fused_core, operation for operation, for the panel kernel
+// (dcor_subgpanel.hip).  WAVE: one wave per replicate (ws), else one workgroup (sel); every thread
+// of it calls.
+template <bool WAVE, int VPL>
+__device__ __forceinline__ void subg_int_finish(const SubgConst& c, uint32_t rep, const DD& sU,
+                                                const DD& sU2, double lapz, SelScratch* sel,
+                                                WaveMix<VPL>* ws, double* o) {
+  const DD mU = dd_div_d(sU, c.nd);
+  const double rho = (mU.hi + mU.lo) + c.s_central * lapz;             // :91
+  const double sd = sqrt(dd_var(sU, sU2, c.nd));
+  const double se_norm = sqrt(sd * sd + c.sn2x2);                      // :99
+  const double cstar = 2.0 / (c.sqrt_n * sd * c.eps_r);                // :100
+  double q;
+  if constexpr (WAVE) q = wave_mixquant_fused<VPL>(c.mix, cstar, rep, c.k0, c.k1, ws);
+  else q = mixquant_fused(c.mix, cstar, rep, c.k0, c.k1, sel);
+  const double width = q * se_norm / c.sqrt_n;                         // :101
+  o[3] = rho;
+  o[4] = rmax(rho - width, -1.0);
+  o[5] = rmin(rho + width, 1.0);
+}
+
 
 }  // namespace dcor

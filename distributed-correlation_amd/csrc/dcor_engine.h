@@ -392,6 +392,59 @@ int launch_hrs_table(const PrematSubgConst& c, const double* D, int64_t p, int64
                      double* cols, int64_t npad, const HrsPairSegConst* tab, int nseg, int64_t items,
                      int64_t max_km, void* part, dcor_rep_out* out, void* stream);
 
+// ---- sub-G simulation estimators on a shared panel (dcor_subg_panel_launch; dcor_subgpanel.hip) ----
+// One segment of a sub-G panel call: the part of SubgConst that depends on the segment's (eps1,
+// eps2) (make_subg's values, unchanged; ls follows the sender's eta), its Philox key and its place
+// in the call.  The launch's device table holds the segments with reps > 0 in call order, so
+// `first` is strictly increasing; n, nd, sqrt_n, the NI clips l1 / l2, crit and mix are the same for
+// every segment and stay a kernel argument.
+struct SubgSegConst {
+  int64_t k;
+  int32_t m, md_pow2, sender_is_X;
+  int32_t m_slot;                // the segment's entry in the call's list of distinct m
+  double md, kd, inv_md;
+  double bx, by, m_over_k, sqrt_k;
+  double ls, lr, bs, s_central, sn2x2, eps_r;
+  uint32_t k0, k1;               // Philox key (seed lo, hi)
+  uint32_t rep_begin, pad;
+  int64_t mean_off;              // its m's first batch mean in the call's means (= its slot's off)
+  int64_t first;                 // the segment's first work item: the sum of the reps before it
+  int64_t out_row;
+};
+static_assert(sizeof(SubgSegConst) == 168, "the sub-G panel's device table stride");
+// One distinct batch size m of a call: its k batch means (X-bar_j, Y-bar_j) of the clipped samples
+// start at means[off]; the slots are in order of first use and off is the sum of the k before.
+struct SubgMeanSlot {
+  int64_t k, off;
+  int32_t m, md_pow2;
+  double md, inv_md;
+};
+static_assert(sizeof(SubgMeanSlot) == 40, "the sub-G panel's slot table stride");
+// Sub-G panel scratch: the segment table | the slot table | the batch means of every slot (16 B
+// per batch) | the packed panel (x, y) of n rounded up to npad (a multiple of 4; zeros from n on).
+// Every region starts 256-B aligned when the base is.  nmeans: the sum of the slots' k.
+struct SubgPanelLayout {
+  int64_t npad;
+  size_t tab_off = 0, slot_off, means_off, pack_off, bytes;
+  SubgPanelLayout(int64_t nseg, int64_t nslots, int64_t nmeans, int64_t n)
+      : npad((n + 3) & ~(int64_t)3),
+        slot_off(al256((size_t)nseg * sizeof(SubgSegConst))),
+        means_off(slot_off + al256((size_t)nslots * sizeof(SubgMeanSlot))),
+        pack_off(means_off + al256((size_t)nmeans * sizeof(double2))),
+        bytes(pack_off + (size_t)npad * sizeof(double2)) {}
+  SubgSegConst* tab(void* base) const { return (SubgSegConst*)((char*)base + tab_off); }
+  SubgMeanSlot* slots(void* base) const { return (SubgMeanSlot*)((char*)base + slot_off); }
+  double2* means(void* base) const { return (double2*)((char*)base + means_off); }
+  double2* xy(void* base) const { return (double2*)((char*)base + pack_off); }
+};
+// The preparation launch (the packed panel and every slot's batch means, subg_fused_core's
+// arithmetic) and the replicate launch over `items` replicates of the nseg >= 1 segments in `tab`
+// (device).  c: any segment's constants (n, nd, sqrt_n, l1, l2, crit, mix are call-wide).  Item i of
+// segment s is replicate s.rep_begin + (i - s.first), record out[s.out_row + (i - s.first)].
+int launch_subg_panel(const SubgConst& c, const double* X, const double* Y, const SubgMeanSlot* slots,
+                      int nslots, double2* means, double2* xy, int64_t npad, const SubgSegConst* tab,
+                      int nseg, int64_t items, dcor_rep_out* out, void* stream);
+
 // ---- sign family on a shared panel (dcor_sign_panel_launch; dcor_signpanel.hip) ----
 // One segment of a sign-panel call: make_sign's constants for the segment's (eps1, eps2) with its
 // Philox key in s.k0 / s.k1 and its first replicate in s.rep_begin, and its place in the call.

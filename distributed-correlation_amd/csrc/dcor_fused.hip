@@ -195,38 +195,8 @@ __device__ __forceinline__ void sample_lap(const DgpConst& g, uint32_t i, uint32
 }
 
 // word, FlipGen, mixquant_fused, scalar_laplace, sign_finish: dcor_common.h (shared with the
-// sign-family panel kernel of dcor_signpanel.hip).
-
-// Wave-level mixquant from Philox (one replicate per wave): the same elements as
-// mixquant_fused, VPL keys per lane, written to the wave's LDS and selected there.
-template <int VPL>
-struct WaveMix {
-  double keys[64 * VPL];
-  WaveSelL sel;
-};
-
-template <int VPL>
-__device__ __forceinline__ double wave_mixquant_fused(const MixConst& mx, double c, uint32_t rep,
-                                                      uint32_t k0, uint32_t k1, WaveMix<VPL>* ws) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int s = 0; s < VPL / 2; ++s) {
-    const int b = lane + 64 * s;  // Philox block b -> elements 2b, 2b+1
-    double v0 = dnan(), v1 = dnan();
-    if (2 * b < mx.nsim) {
-      const U4 wz = draw((uint32_t)b, rep, DCOR_SITE_MIX_Z, k0, k1);
-      const U4 wl = draw((uint32_t)b, rep, DCOR_SITE_MIX_L, k0, k1);
-      double z0, z1;
-      normal_pair(wz, &z0, &z1);
-      v0 = z0 + c * unit_laplace(u53(wl.w0, wl.w1));
-      if (2 * b + 1 < mx.nsim) v1 = z1 + c * unit_laplace(u53(wl.w2, wl.w3));
-    }
-    ws->keys[lane + 64 * (2 * s)] = v0;
-    ws->keys[lane + 64 * (2 * s + 1)] = v1;
-  }
-  wave_sync();
-  return wave_select_lds<VPL>(ws->keys, mx.pos, &ws->sel);
-}
+// sign-family panel kernel of dcor_signpanel.hip); WaveMix, wave_mixquant_fused: dcor_common.h too
+// (shared with the sub-G panel kernel of dcor_subgpanel.hip).
 
 // ======================================== fused sign family, one pass (hot) ===
 // Pass 1 generates each sample once: the DP-mean sums of clip(x), clip(y) (vert-cor.R:
@@ -1878,6 +1848,8 @@ __device__ __forceinline__ void subg_fused_core(const SubgConst& c, uint32_t rep
   }
   double o[6];
   ni_subg_result(c, d5[0], d5[1], d5[2], o);
+  // the INT tail: subg_int_finish (dcor_common.h) is this code for the panel kernel, kept apart
+  // because calling it from here changes this kernel's register allocation and schedule
   const DD mU = dd_div_d(d5[3], c.nd);
   const double rho = (mU.hi + mU.lo) + c.s_central * lapz;             // :91
   const double sd = sqrt(dd_var(d5[3], d5[4], c.nd));

@@ -1,6 +1,6 @@
 // dcor_plan.cpp -- the device-free half of the host side (dcor_plan.h): the error reporter, the
 // argument checks of the reference's stopifnot() calls, every data-independent scalar of the
-// estimators (R operation order, cited), and the segment planners of the five segment-list
+// estimators (R operation order, cited), and the segment planners of the six segment-list
 // entries.  No HIP: this file and the headers it includes compile with a host compiler alone.
 #include "dcor_plan.h"
 
@@ -221,9 +221,13 @@ namespace {
 template <class Seg> bool eps_ok(const Seg& g) { return g.eps1 > 0.0 && g.eps2 > 0.0; }
 bool eps_ok(const dcor_hrs_segment& g) { return g.eps > 0.0; }
 bool eps_ok(const dcor_hrs_pair_segment& g) { return g.eps > 0.0; }
+bool eps_ok(const dcor_subg_segment& g) {
+  return g.eps1 > 0.0 && g.eps2 > 0.0 && std::isfinite(g.eps1) && std::isfinite(g.eps2);
+}
 template <class Seg> const char* eps_names(const Seg&) { return "eps1, eps2"; }
 const char* eps_names(const dcor_hrs_segment&) { return "eps"; }
 const char* eps_names(const dcor_hrs_pair_segment&) { return "eps"; }
+const char* eps_names(const dcor_subg_segment&) { return "finite eps1, eps2"; }
 template <class Seg> int check_columns(const char*, const Seg&, int64_t, int64_t) { return DCOR_OK; }
 template <class Seg> int columns_in_range(const char* entry, const Seg& g, int64_t i, int64_t p) {
   if (g.col_x < 0 || g.col_x >= p || g.col_y < 0 || g.col_y >= p)
@@ -467,6 +471,59 @@ int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* se
   if (!HrsTableLayout(*items, (int64_t)tab.size(), t->n, t->p).ok)
     return fail(DCOR_EINVAL, "hrs_table: scratch bytes overflow (p = %lld, n = %lld)", (long long)t->p,
                 (long long)t->n);
+  return DCOR_OK;
+}
+
+int plan_subg_panel(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs, int64_t nseg,
+                    std::vector<SubgSegConst>& tab, std::vector<SubgMeanSlot>& slots, SubgConst* c0,
+                    int64_t* items) {
+  *items = 0;
+  if (!p->X || !p->Y) return fail(DCOR_EINVAL, "subg_panel: null argument (X, Y)");
+  if (((uintptr_t)p->X | (uintptr_t)p->Y) & 7)
+    return fail(DCOR_EINVAL, "subg_panel: X and Y must be aligned to 8 bytes");
+  if (p->n < 1 || p->n > 0x7fffffffLL)
+    return fail(DCOR_EINVAL, "subg_panel: n must be in [1, 2^31) (got %lld)", (long long)p->n);
+  if (!(p->eta1 > 0.0) || !(p->eta2 > 0.0) || !std::isfinite(p->eta1) || !std::isfinite(p->eta2))
+    return fail(DCOR_EINVAL, "subg_panel: eta1, eta2 must be finite and > 0 (got %g, %g)", p->eta1, p->eta2);
+  {  // alpha and nsim, as every segment's make_subg would refuse them
+    MixConst mx;
+    if (int st = check_common(p->n, 1.0, 1.0, p->alpha)) return st;
+    if (int st = make_mix(p->nsim, p->alpha, mx)) return st;
+  }
+  if (int st = segment_heads("subg_panel", segs, nseg, 0, items)) return st;
+  // every segment's launch constants: make_subg's own, the simulation variant (hrs = 0, no override)
+  int64_t first = 0, nmeans = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_subg_segment& g = segs[i];
+    SubgConst a;
+    if (int st = make_subg(p->n, g.eps1, g.eps2, p->eta1, p->eta2, p->alpha, 0, NAN, NAN, NAN, NAN, NAN,
+                           NAN, p->nsim, a, nullptr, nullptr))
+      return st;
+    if (g.reps == 0) continue;
+    if (tab.empty()) *c0 = a;
+    size_t d = 0;
+    while (d < slots.size() && slots[d].m != a.m) ++d;
+    if (d == slots.size()) {   // a batch size not seen before: its k means follow the others'
+      SubgMeanSlot sl;
+      std::memset(&sl, 0, sizeof(sl));
+      sl.k = a.k; sl.off = nmeans; sl.m = a.m; sl.md_pow2 = a.md_pow2; sl.md = a.md; sl.inv_md = a.inv_md;
+      nmeans += a.k;
+      slots.push_back(sl);
+    }
+    SubgSegConst t;
+    std::memset(&t, 0, sizeof(t));
+    t.k = a.k; t.m = a.m; t.md_pow2 = a.md_pow2; t.sender_is_X = a.sender_is_X;
+    t.m_slot = (int32_t)d;
+    t.md = a.md; t.kd = a.kd; t.inv_md = a.inv_md;
+    t.bx = a.bx; t.by = a.by; t.m_over_k = a.m_over_k; t.sqrt_k = a.sqrt_k;
+    t.ls = a.ls; t.lr = a.lr; t.bs = a.bs; t.s_central = a.s_central; t.sn2x2 = a.sn2x2; t.eps_r = a.eps_r;
+    t.k0 = (uint32_t)g.seed; t.k1 = (uint32_t)(g.seed >> 32);
+    t.rep_begin = (uint32_t)g.rep_begin;
+    t.mean_off = slots[d].off;
+    t.first = first; t.out_row = g.out_row;
+    first += g.reps;
+    tab.push_back(t);
+  }
   return DCOR_OK;
 }
 

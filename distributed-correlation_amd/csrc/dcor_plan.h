@@ -1,5 +1,5 @@
 // dcor_plan.h -- the host decisions that need no device: the error reporter, the argument checks,
-// every launch constant (R operation order, cited) and the segment planners of the five
+// every launch constant (R operation order, cited) and the segment planners of the six
 // segment-list entries.  Plain C++: neither this header nor dcor_plan.cpp includes the HIP
 // runtime, so the unit compiles, runs and is sanitized with a host compiler alone
 // (tests/host/plan_check.cpp).  Not part of the ABI.
@@ -119,6 +119,17 @@ dcor_premat_subg hrs_pair_desc(const dcor_hrs_table_desc& t, const dcor_hrs_pair
 // items: the call's replicates; max_km: the largest k m of the kept segments.
 int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs, int64_t nseg,
                    std::vector<HrsPairSegConst>& tab, int64_t* items, int64_t* max_km);
+
+// dcor_subg_panel_launch.  Every check of the entry after its null checks of p, segs and d_out, in
+// the header's order (X and Y, n, eta1 and eta2, alpha, nsim, then the segments' fields and ranges,
+// the replicate cap, every segment's constants), then the table: a kept segment's record holds,
+// field for field, what make_subg yields for (n, eps1, eps2, eta1, eta2, alpha, hrs = 0, nsim).
+// slots: the distinct batch sizes m of the kept segments in order of first use (a record's m_slot
+// names its entry, mean_off that entry's off); c0: the first kept segment's constants (the
+// call-wide ones are read from it); items: the call's replicates.
+int plan_subg_panel(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs, int64_t nseg,
+                    std::vector<SubgSegConst>& tab, std::vector<SubgMeanSlot>& slots, SubgConst* c0,
+                    int64_t* items);
 
 #pragma GCC visibility pop
 

@@ -15,3 +15,4 @@ from .sim import (CellSpec, headline_cell, paper_grid, run_cell, run_grid, run_s
 __version__ = "0.1.0"
 from . import rstream  # noqa: F401,E402
 from . import signpanel  # noqa: F401,E402
+from . import subgpanel  # noqa: F401,E402

@@ -107,6 +107,18 @@ class SignSegment(C.Structure):
                 ("rep_begin", C.c_int64), ("reps", C.c_int64), ("out_row", C.c_int64)]
 
 
+class SubgPanelDesc(C.Structure):
+    """dcor_subg_panel_desc (include/dcor.h): the shared panel and the call-wide settings."""
+    _fields_ = [("n", C.c_int64), ("X", _P), ("Y", _P), ("eta1", C.c_double), ("eta2", C.c_double),
+                ("alpha", C.c_double), ("nsim", C.c_int64)]
+
+
+class SubgSegment(C.Structure):
+    """dcor_subg_segment (include/dcor.h): one (eps pair, key, replicate range, output row)."""
+    _fields_ = [("eps1", C.c_double), ("eps2", C.c_double), ("seed", C.c_uint64),
+                ("rep_begin", C.c_int64), ("reps", C.c_int64), ("out_row", C.c_int64)]
+
+
 class SignTableDesc(C.Structure):
     """dcor_sign_table_desc (include/dcor.h): the shared table (p columns of n samples, ld apart)
     and the call-wide settings."""
@@ -197,6 +209,8 @@ SIGNATURES = {
                                          _P, _P]),
     "dcor_hrs_table_launch": (C.c_int, [C.POINTER(HrsTableDesc), C.POINTER(HrsPairSegment), C.c_int64,
                                         _P, _P]),
+    "dcor_subg_panel_launch": (C.c_int, [C.POINTER(SubgPanelDesc), C.POINTER(SubgSegment), C.c_int64,
+                                         _P, _P]),
     "dcor_batch_geometry": (C.c_int, [C.c_int64, C.c_double, C.c_double, C.c_int, C.c_int, _I64]),
     "dcor_ci_ni_signbatch": (C.c_int, [_D, _D, C.c_int64, C.c_double, C.c_double, C.c_double,
                                        C.c_int, _D, _D, _D, _D]),

@@ -246,6 +246,28 @@ def sign_table_distributed(D, segs, group=None, **kw):
     return gather_rows(local, counts, group)
 
 
+def subg_panel_distributed(X, Y, segs, group=None, **kw):
+    """dcor.subgpanel.sweep_segments over G ranks, as sign_table_distributed: the flattened (segment,
+    replicate) space of segs [(eps1, eps2, seed, rep_begin, reps), ...] is split into contiguous
+    per-rank ranges (segment_shard), each rank runs its pieces -- the segment's eps pair and key,
+    rep_begin moved on by the piece's offset -- in one native call, and the records are all-gathered
+    in rank order.  A record depends only on (panel, eta, eps1, eps2, seed, replicate), so the
+    [sum(reps), 6] result, identical on all ranks, equals one process's sweep_segments(X, Y, segs)
+    byte for byte."""
+    import torch.distributed as dist
+
+    from . import subgpanel
+    segs = list(segs)
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    seg_reps = [int(s[4]) for s in segs]
+    if sum(seg_reps) == 0:   # the same on every rank: nothing to run or gather
+        return np.zeros((0, 6))
+    mine = [(*segs[j][:3], int(segs[j][3]) + r0, c) for j, r0, c in segment_shard(seg_reps, rank, world)]
+    local = subgpanel.sweep_segments(X, Y, mine, **kw) if mine else np.zeros((0, 6))
+    counts = [shard(sum(seg_reps), r, world)[1] for r in range(world)]
+    return gather_rows(local, counts, group)
+
+
 def hrs_table_distributed(Z, lam, segs, group=None, **kw):
     """dcor.hrs.table_segments over G ranks, as sign_table_distributed: the flattened (segment,
     replicate) space of segs [(col_x, col_y, eps, seed_ni, seed_int, rep_begin, reps), ...] is split

@@ -514,6 +514,57 @@ typedef struct dcor_hrs_pair_segment {
 int dcor_hrs_table_launch(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs,
                           int64_t nseg, dcor_rep_out* d_out, void* stream);
 
+/* The sub-Gaussian estimators of the simulation (correlation_NI_subG + ci_INT_subG,
+ * ver-cor-subG.R:25-108: contiguous batches, lambda_n / lambda_INT_n, any (eps1, eps2), either
+ * sender) on the caller's own (X, Y), prepared once and shared by every replicate, with every noise
+ * draw made inside the kernel: the sub-G counterpart of dcor_sign_panel_launch, and of running
+ * ver-cor-subG.R:179-195 on one data set.  Replicate rep_begin + j of a segment goes to
+ * d_out[out_row + j].  The estimators are those of dcor_premat_subg_launch with hrs = 0 (every
+ * lam NaN): m = ceil(8 / (eps1 eps2)) capped at n, k = floor(n / m) >= 1, the samples past k m
+ * enter INT only, the sender is X iff eps1 >= eps2 and the other variable is not clipped.  One
+ * preparation launch (the panel packed as (x, y) pairs, and for every distinct batch size m of the
+ * call the k batch means of the samples clipped at lambda_n(n, eta1) / lambda_n(n, eta2): the clips
+ * do not depend on the data and the batches are contiguous, so a batch's two clipped means are the
+ * same in every replicate; they are the bits the fused engine forms) and one replicate launch
+ * cover every segment, whatever its (eps1, eps2).
+ *
+ * Draw contract: the fused sub-G engine's (the DCOR_SITE_* list below) with the DGP samples
+ * replaced by the panel.  Philox key = the segment's seed, counter = (index, replicate, site, 0):
+ *   DCOR_SITE_SCALAR  block 4, words 0,1: the central Laplace (ver-cor-subG.R:91);
+ *   DCOR_SITE_NI_LAP  block j: batch j's unit Laplace for X (w0, w1) and Y (w2, w3);
+ *   DCOR_SITE_DGP_B   block i, words 2,3: sample i's local unit Laplace (words 0,1 unused here);
+ *   DCOR_SITE_MIX_Z, DCOR_SITE_MIX_L: mixquant's normals and unit Laplace, 2 per block.
+ * So a panel replicate uses the draws of the same replicate of dcor_sim_launch on a sub-G cell with
+ * that seed: on that replicate's dcor_dgp_launch samples the two records agree to rounding.  A
+ * record depends only on (panel, eta1, eta2, eps1, eps2, seed, replicate), never on the segment
+ * split, the order of segments, out_row or the launch, so any sharding over calls or GPUs by
+ * rep_begin is exact.
+ *
+ * NaN: a NaN among the first k m samples makes the NI columns NaN, one anywhere makes the INT
+ * columns NaN (as dcor_premat_subg_launch with hrs = 0, and R).
+ * Checks, all before anything is enqueued and before any device access (an invalid call returns
+ * its code and leaves d_out untouched; dcor_last_error names the segment): non-null p, X, Y, segs,
+ * d_out; X, Y aligned to 8 bytes; 1 <= n < 2^31; eta1, eta2 > 0 and finite; alpha, nsim (<= 2048)
+ * as dcor_sim_launch; per segment eps1, eps2 > 0 and finite, reps, rep_begin, out_row >= 0,
+ * rep_begin + reps <= 2^32; at most 2^31 - 1 replicates per call.  nseg == 0 or no replicates at
+ * all returns DCOR_OK with no device work.  Asynchronous on `stream`, no host synchronisation;
+ * scratch is stream-ordered (16 B per sample, 16 B per batch and distinct m, the segment table) --
+ * no noise array; X, Y and segs are borrowed for the call only (X, Y until the call's work on
+ * `stream` has run). */
+typedef struct dcor_subg_panel_desc {
+  int64_t n;
+  const double *X, *Y;   /* DEVICE, [n], shared by every replicate; borrowed for the call */
+  double eta1, eta2, alpha;
+  int64_t nsim;
+} dcor_subg_panel_desc;
+typedef struct dcor_subg_segment {
+  double eps1, eps2;
+  uint64_t seed;
+  int64_t rep_begin, reps, out_row;
+} dcor_subg_segment;
+int dcor_subg_panel_launch(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs,
+                           int64_t nseg, dcor_rep_out* d_out, void* stream);
+
 int dcor_premat_sign_launch(const dcor_premat_sign* d, dcor_rep_out* d_out, void* stream);
 int dcor_premat_subg_launch(const dcor_premat_subg* d, dcor_rep_out* d_out, void* stream);
 
