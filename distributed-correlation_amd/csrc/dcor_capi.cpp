@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
@@ -100,15 +101,22 @@ static int with_scratch(const char* entry, const char* kind, size_t bytes, void*
   return e;
 }
 
-// with_scratch for a launch driven by a segment table: `tab` copied to buf + tab_off, then
-// `launch(buf)` (hipError_t as int).
+// A further pageable host block of a table launch: `bytes` from `src` to buf + off.
+struct HostBlock { size_t off; const void* src; size_t bytes; };
+
+// with_scratch for a launch driven by a segment table: `tab` copied to buf + tab_off, the blocks of
+// `more` after it in their order, then `launch(buf)` (hipError_t as int).
 template <class T, class Launch>
 static int with_table(const char* entry, size_t bytes, const std::vector<T>& tab, size_t tab_off,
-                      void* stream, Launch launch, bool counted = true) {
+                      void* stream, Launch launch, bool counted = true,
+                      std::initializer_list<HostBlock> more = {}) {
   return with_scratch(entry, "scratch", bytes, stream, [&](void* buf) {
-    // from pageable memory: the copy has left `tab` when the call returns
+    // from pageable memory: a copy has left its source when the call returns
     int rc = (int)hipMemcpyAsync((char*)buf + tab_off, tab.data(), tab.size() * sizeof(T),
                                  hipMemcpyHostToDevice, (hipStream_t)stream);
+    for (const HostBlock& b : more)
+      if (!rc) rc = (int)hipMemcpyAsync((char*)buf + b.off, b.src, b.bytes, hipMemcpyHostToDevice,
+                                        (hipStream_t)stream);
     if (!rc) rc = launch(buf);
     return rc ? fail(DCOR_EHIP, "%s launch: %s", entry, hipGetErrorString((hipError_t)rc)) : DCOR_OK;
   }, counted);
@@ -1078,10 +1086,16 @@ int dcor_hrs_fused_sweep_launch(const dcor_premat_subg* base, const dcor_panel* 
   });
 }
 
+// The segment entries' argument check: the description always, the segments and the output when
+// there are segments.
+static int seg_args(const char* entry, const void* desc, const void* segs, int64_t nseg, const void* d_out) {
+  if (!desc || nseg < 0 || (nseg > 0 && (!segs || !d_out))) return fail(DCOR_EINVAL, "%s: null argument", entry);
+  return DCOR_OK;
+}
+
 int dcor_sign_panel_launch(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream) {
-  if (!p || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
-    return fail(DCOR_EINVAL, "sign_panel: null argument");
+  if (int st = seg_args("sign_panel", p, segs, nseg, d_out)) return st;
   if (nseg == 0) return DCOR_OK;   // nothing to run
   std::vector<SignSegConst> tab;
   int64_t items = 0;
@@ -1097,8 +1111,7 @@ int dcor_sign_panel_launch(const dcor_sign_panel_desc* p, const dcor_sign_segmen
 
 int dcor_sign_table_launch(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream) {
-  if (!t || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
-    return fail(DCOR_EINVAL, "sign_table: null argument");
+  if (int st = seg_args("sign_table", t, segs, nseg, d_out)) return st;
   if (nseg == 0) return DCOR_OK;   // nothing to run
   std::vector<SignPairSegConst> tab;
   int64_t items = 0;
@@ -1114,8 +1127,7 @@ int dcor_sign_table_launch(const dcor_sign_table_desc* t, const dcor_sign_pair_s
 
 int dcor_hrs_table_launch(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs,
                           int64_t nseg, dcor_rep_out* d_out, void* stream) {
-  if (!t || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
-    return fail(DCOR_EINVAL, "hrs_table: null argument");
+  if (int st = seg_args("hrs_table", t, segs, nseg, d_out)) return st;
   if (nseg == 0) return DCOR_OK;   // nothing to run
   std::vector<HrsPairSegConst> tab;
   int64_t items = 0, max_km = 0;
@@ -1134,19 +1146,14 @@ int dcor_hrs_table_launch(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segm
   p.X = p.Y = nullptr;
   const HrsTableLayout lay(items, (int64_t)tab.size(), t->n, t->p);
   return with_table("hrs_table", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
-    // from pageable memory, as the table: the copy has left t->lam when the call returns
-    if (int rc = (int)hipMemcpyAsync(lay.lam(buf), t->lam, (size_t)t->p * sizeof(double),
-                                     hipMemcpyHostToDevice, (hipStream_t)stream))
-      return rc;
     return launch_hrs_table(p, t->D, t->p, t->ld, lay.lam(buf), lay.cols(buf), lay.npad, lay.tab(buf),
                             (int)tab.size(), items, max_km, buf, d_out, stream);
-  }, false);
+  }, false, {{lay.lam_off, t->lam, (size_t)t->p * sizeof(double)}});
 }
 
 int dcor_subg_panel_launch(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream) {
-  if (!p || nseg < 0 || (nseg > 0 && (!segs || !d_out)))
-    return fail(DCOR_EINVAL, "subg_panel: null argument");
+  if (int st = seg_args("subg_panel", p, segs, nseg, d_out)) return st;
   if (nseg == 0) return DCOR_OK;   // nothing to run
   std::vector<SubgSegConst> tab;
   std::vector<SubgMeanSlot> slots;
@@ -1158,13 +1165,9 @@ int dcor_subg_panel_launch(const dcor_subg_panel_desc* p, const dcor_subg_segmen
   const int64_t nmeans = slots.back().off + slots.back().k;
   const SubgPanelLayout lay((int64_t)tab.size(), (int64_t)slots.size(), nmeans, p->n);
   return with_table("subg_panel", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
-    // from pageable memory, as the table: the copy has left `slots` when the call returns
-    if (int rc = (int)hipMemcpyAsync(lay.slots(buf), slots.data(), slots.size() * sizeof(SubgMeanSlot),
-                                     hipMemcpyHostToDevice, (hipStream_t)stream))
-      return rc;
     return launch_subg_panel(c0, p->X, p->Y, lay.slots(buf), (int)slots.size(), lay.means(buf), lay.xy(buf),
                              lay.npad, lay.tab(buf), (int)tab.size(), items, d_out, stream);
-  }, false);
+  }, false, {{lay.slot_off, slots.data(), slots.size() * sizeof(SubgMeanSlot)}});
 }
 
 int dcor_panel_dict_probe(const double* d_X, const double* d_Y, int64_t n, int* ok) {

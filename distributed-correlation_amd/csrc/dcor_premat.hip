@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "dcor_common.h"
+#include "dcor_segtab.h"
 
 namespace dcor {
 
@@ -2037,23 +2038,11 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_fused_epilogue(PrematSubgCon
 // address space at workgroup-uniform addresses: scalar loads into SGPRs, once per segment a
 // workgroup enters, never per lane and never inside the replicate's loops.
 // The table's record is HrsSegConst (the sweep) or HrsPairSegConst (the table entry, which adds the
-// segment's two columns): one cursor, search and load for both.
-template <class Seg> using HrsSegTab = const __attribute__((address_space(4))) Seg*;
-
-// The last segment whose first item is <= it (`first` is strictly increasing, tab[0].first = 0).
-template <class Seg>
-__device__ __forceinline__ int hrs_seg_find(HrsSegTab<Seg> tab, int nseg, int64_t it) {
-  int lo = 0, hi = nseg - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].first <= it) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
+// segment's two columns): one load for both, the search and the cursor are dcor_segtab.h's.
 
 // Segment s's constants over the sweep-wide ones in p, its keys into hk.
 template <class Seg>
-__device__ __forceinline__ void hrs_seg_load(HrsSegTab<Seg> tab, int s, PrematSubgConst& p, HrsKeys& hk) {
+__device__ __forceinline__ void hrs_seg_load(SegTab<Seg> tab, int s, PrematSubgConst& p, HrsKeys& hk) {
   SubgConst& c = p.s;
   c.k = tab[s].k; c.m = tab[s].m; c.md_pow2 = tab[s].md_pow2;
   c.md = tab[s].md; c.kd = tab[s].kd; c.inv_md = tab[s].inv_md;
@@ -2063,22 +2052,6 @@ __device__ __forceinline__ void hrs_seg_load(HrsSegTab<Seg> tab, int s, PrematSu
   hk.ni0 = tab[s].ni0; hk.ni1 = tab[s].ni1; hk.in0 = tab[s].in0; hk.in1 = tab[s].in1;
   hk.rep_begin = tab[s].rep_begin;
 }
-
-// A workgroup's items ascend, so it re-reads the table only when an item passes the end of the
-// segment it holds.  seek returns the segment it loaded, or -1 when the held one still covers `it`.
-struct HrsSegCursor {
-  int64_t first = 0, end = 0;   // items [first, end) belong to the loaded segment
-  template <class Seg>
-  __device__ __forceinline__ int seek(HrsSegTab<Seg> tab, int nseg, int64_t items, int64_t it,
-                                      PrematSubgConst& p, HrsKeys& hk) {
-    if (it < end) return -1;
-    const int s = __builtin_amdgcn_readfirstlane(hrs_seg_find(tab, nseg, it));
-    hrs_seg_load(tab, s, p, hk);
-    first = tab[s].first;
-    end = s + 1 < nseg ? tab[s + 1].first : items;
-    return s;
-  }
-};
 
 template <int WPE>
 __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_sweep_fused(PrematSubgConst p, int pa, int pc,
@@ -2092,12 +2065,12 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_sweep_fused(PrematSubgCons
                                                                  int64_t scr_stride) {
   extern __shared__ double dsm[];
   const HrsLds L = hrs_fused_setup(p, codes_g, dict_g, dsm);
-  const HrsSegTab<HrsSegConst> tab = (HrsSegTab<HrsSegConst>)tab_g;
+  const SegTab<HrsSegConst> tab = (SegTab<HrsSegConst>)tab_g;
   HrsKeys hk{0, 0, 0, 0, 0, pa, pc};
-  HrsSegCursor cur;
+  SegCursor cur;
   int par = 0;
   for (int64_t it = blockIdx.x; it < items; it += gridDim.x, par ^= 1) {
-    cur.seek(tab, nseg, items, it, p, hk);
+    cur.seek(tab, nseg, items, it, [&](int s) { hrs_seg_load(tab, s, p, hk); });
     hrs_fused_item(p, hk, hk.rep_begin + (uint32_t)(it - cur.first), L.dX, L.dY, L.dS, L.dO, L.cod,
                    scr + (int64_t)blockIdx.x * scr_stride, L.red, par, part + it);
   }
@@ -2111,12 +2084,12 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_sweep_fused_l2(PrematSubgC
   extern __shared__ double dsm[];
   double* red = dsm;
   uint16_t* gs = reinterpret_cast<uint16_t*>(dsm + 20 * DICT_NW);  // the largest k m of the segments
-  const HrsSegTab<HrsSegConst> tab = (HrsSegTab<HrsSegConst>)tab_g;
+  const SegTab<HrsSegConst> tab = (SegTab<HrsSegConst>)tab_g;
   HrsKeys hk{0, 0, 0, 0, 0, pa, pc};
-  HrsSegCursor cur;
+  SegCursor cur;
   int par = 0;
   for (int64_t it = blockIdx.x; it < items; it += gridDim.x, par ^= 1) {
-    cur.seek(tab, nseg, items, it, p, hk);
+    cur.seek(tab, nseg, items, it, [&](int s) { hrs_seg_load(tab, s, p, hk); });
     hrs_fused_l2_item(p, hk, hk.rep_begin + (uint32_t)(it - cur.first), HrsPackedLoad{p.xyc, p.soc}, gs,
                       red, par, part + it);
   }
@@ -2131,10 +2104,10 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_sweep_fused_epilogue(PrematS
                                                                          dcor_rep_out* out) {
   __shared__ SelScratch sel;
   __shared__ double bc[2];
-  const HrsSegTab<Seg> tab = (HrsSegTab<Seg>)tab_g;
+  const SegTab<Seg> tab = (SegTab<Seg>)tab_g;
   const int64_t r = blockIdx.x;
   HrsKeys hk{0, 0, 0, 0, 0, 0, 0};   // the epilogue draws no permutation: pa, pc unused
-  const int s = __builtin_amdgcn_readfirstlane(hrs_seg_find(tab, nseg, r));
+  const int s = __builtin_amdgcn_readfirstlane(seg_find(tab, nseg, r));
   hrs_seg_load(tab, s, p, hk);
   const int64_t j = r - tab[s].first;
   hrs_fused_epilogue_item(p, hk, hk.rep_begin + (uint32_t)j, r, part, out + tab[s].out_row + j, sel, bc);
@@ -2183,17 +2156,17 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_table(PrematSubgConst p, i
   extern __shared__ double dsm[];
   double* red = dsm;
   uint16_t* gs = reinterpret_cast<uint16_t*>(dsm + 20 * DICT_NW);  // the largest k m of the segments
-  const HrsSegTab<HrsPairSegConst> tab = (HrsSegTab<HrsPairSegConst>)tab_g;
+  const SegTab<HrsPairSegConst> tab = (SegTab<HrsPairSegConst>)tab_g;
   HrsKeys hk{0, 0, 0, 0, 0, pa, pc};
-  HrsSegCursor cur;
+  SegCursor cur;
   HrsColumnLoad ld{nullptr, nullptr};   // the pair's columns: no per-pair state but these pointers
   int par = 0;
   for (int64_t it = blockIdx.x; it < items; it += gridDim.x, par ^= 1) {
-    const int s = cur.seek(tab, nseg, items, it, p, hk);
-    if (s >= 0) {   // entered a segment: its columns, at a workgroup-uniform address
+    cur.seek(tab, nseg, items, it, [&](int s) {   // its columns, at a workgroup-uniform address
+      hrs_seg_load(tab, s, p, hk);
       ld.ca = cols + (int64_t)tab[s].col_x * pitch;
       ld.cb = cols + (int64_t)tab[s].col_y * pitch;
-    }
+    });
     hrs_fused_l2_item(p, hk, hk.rep_begin + (uint32_t)(it - cur.first), ld, gs, red, par, part + it);
   }
 }
@@ -2228,6 +2201,21 @@ static void hrs_feistel_split(int64_t n, int* pa, int* pc) {
   *pa = bits / 2; *pc = bits - *pa;
 }
 
+// The HRS streaming kernels' waves-per-SIMD arm (DCOR_HRS_WPE: 6, or 4).
+static int hrs_wpe() { return (int)dcor::variant("DCOR_HRS_WPE").as_int(6, 4, 4); }
+
+// The dynamic LDS of the uncoded-panel streaming kernels (k_hrs_fused_l2, k_hrs_sweep_fused_l2,
+// k_hrs_table): the reduction buffers and a row of km u16 indices.
+static size_t hrs_l2_lds_bytes(int64_t km) {
+  return (size_t)(20 * DICT_NW) * sizeof(double) + (size_t)((km * 2 + 15) / 16) * 16;
+}
+
+// The packed clips of an uncoded panel (c.xyc, c.soc): the same for every replicate, once per call.
+static void launch_xy_pack(const PrematSubgConst& c, void* stream) {
+  hipLaunchKernelGGL(k_premat_xy_pack, dim3((unsigned)((c.s.n + DCOR_BLOCK - 1) / DCOR_BLOCK)),
+                     dim3(DCOR_BLOCK), 0, (hipStream_t)stream, c, (double2*)c.xyc, (double2*)c.soc);
+}
+
 int launch_hrs_fused(const PrematSubgConst& c, uint64_t seed_ni, uint64_t seed_int,
                      int64_t rep_begin, int64_t reps, void* part, dcor_rep_out* out,
                      void* stream) {
@@ -2237,15 +2225,10 @@ int launch_hrs_fused(const PrematSubgConst& c, uint64_t seed_ni, uint64_t seed_i
   hk.in0 = (uint32_t)seed_int; hk.in1 = (uint32_t)(seed_int >> 32);
   hk.rep_begin = (uint32_t)rep_begin;
   hrs_feistel_split(c.s.n, &hk.pa, &hk.pc);
-  const int wsel = (int)dcor::variant("DCOR_HRS_WPE").as_int(6, 4, 4);
+  const int wsel = hrs_wpe();
   const bool l2 = c.xyc != nullptr;  // uncoded panel: packed clips in HBM, indices in LDS
-  const size_t lds = l2 ? (size_t)(20 * DICT_NW) * sizeof(double) +
-                              (size_t)((c.s.k * c.s.m * 2 + 15) / 16) * 16
-                        : premat_dict_lds_bytes(c.s.n);
-  if (l2)
-    hipLaunchKernelGGL(k_premat_xy_pack, dim3((unsigned)((c.s.n + DCOR_BLOCK - 1) / DCOR_BLOCK)),
-                       dim3(DCOR_BLOCK), 0, (hipStream_t)stream, c, (double2*)c.xyc,
-                       (double2*)c.soc);
+  const size_t lds = l2 ? hrs_l2_lds_bytes(c.s.k * c.s.m) : premat_dict_lds_bytes(c.s.n);
+  if (l2) launch_xy_pack(c, stream);
   typedef void (*FusedK)(PrematSubgConst, HrsKeys, const uint16_t*, const double*, int64_t,
                          SubgPartial*, uint16_t*, int64_t);
   typedef void (*FusedL2K)(PrematSubgConst, HrsKeys, int64_t, SubgPartial*);
@@ -2279,14 +2262,10 @@ int launch_hrs_fused_sweep(const PrematSubgConst& c, const HrsSegConst* tab, int
   if (items <= 0 || nseg <= 0) return 0;
   int pa, pc;
   hrs_feistel_split(c.s.n, &pa, &pc);
-  const int wsel = (int)dcor::variant("DCOR_HRS_WPE").as_int(6, 4, 4);
+  const int wsel = hrs_wpe();
   const bool l2 = c.xyc != nullptr;  // uncoded panel: packed clips in HBM, indices in LDS
-  const size_t lds = l2 ? (size_t)(20 * DICT_NW) * sizeof(double) + (size_t)((max_km * 2 + 15) / 16) * 16
-                        : premat_dict_lds_bytes(c.s.n);
-  if (l2)   // the clips are sweep-wide: once per call
-    hipLaunchKernelGGL(k_premat_xy_pack, dim3((unsigned)((c.s.n + DCOR_BLOCK - 1) / DCOR_BLOCK)),
-                       dim3(DCOR_BLOCK), 0, (hipStream_t)stream, c, (double2*)c.xyc,
-                       (double2*)c.soc);
+  const size_t lds = l2 ? hrs_l2_lds_bytes(max_km) : premat_dict_lds_bytes(c.s.n);
+  if (l2) launch_xy_pack(c, stream);   // the clips are sweep-wide
   typedef void (*SweepK)(PrematSubgConst, int, int, const HrsSegConst*, int, const uint16_t*,
                          const double*, int64_t, SubgPartial*, uint16_t*, int64_t);
   typedef void (*SweepL2K)(PrematSubgConst, int, int, const HrsSegConst*, int, int64_t, SubgPartial*);
@@ -2319,9 +2298,8 @@ int launch_hrs_table(const PrematSubgConst& c, const double* D, int64_t p, int64
   if (items <= 0 || nseg <= 0 || p <= 0) return 0;
   int pa, pc;
   hrs_feistel_split(c.s.n, &pa, &pc);
-  const int wsel = (int)dcor::variant("DCOR_HRS_WPE").as_int(6, 4, 4);
-  // k_hrs_sweep_fused_l2's threads and LDS: the reduction buffers and a max_km u16 row
-  const size_t lds = (size_t)(20 * DICT_NW) * sizeof(double) + (size_t)((max_km * 2 + 15) / 16) * 16;
+  const int wsel = hrs_wpe();
+  const size_t lds = hrs_l2_lds_bytes(max_km);   // k_hrs_sweep_fused_l2's threads and LDS
   typedef void (*TableK)(PrematSubgConst, int, int, const HrsPairSegConst*, int, int64_t, const double*,
                          int64_t, SubgPartial*);
   const TableK kern = wsel == 4 ? k_hrs_table<4> : k_hrs_table<6>;
@@ -2446,9 +2424,7 @@ int launch_premat_subg(const PrematSubgConst& c0, int64_t reps, void* part, dcor
     // by element), so a replicate's bits do not either.
     const bool tiled = c.dict_built != 2 && tiled_enabled() && c.s.m == 2 && (c.s.k & 1) == 0 &&
                        c.s.k >= 2 && c.s.n < 65536;
-    hipLaunchKernelGGL(k_premat_xy_pack, dim3((unsigned)((c.s.n + DCOR_BLOCK - 1) / DCOR_BLOCK)),
-                       dim3(DCOR_BLOCK), 0, (hipStream_t)stream, c, (double2*)c.xyc,
-                       (double2*)c.soc);
+    launch_xy_pack(c, stream);
     if (tiled) {
       // the INT sums in k_premat_subg_int: on the auxiliary stream when the caller gave one
       const int im = tiled_int_mode();

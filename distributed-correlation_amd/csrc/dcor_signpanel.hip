@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dcor_common.h"
+#include "dcor_segtab.h"
 
 namespace dcor {
 
@@ -113,19 +114,6 @@ __global__ __launch_bounds__(SP_PREP_NT) void k_sign_table_prep(const double* __
 
 #define SP_CAP 4096   // LDS batch counters per pass (16 KB)
 #define SP_PACK_M 32767  // up to this m a batch's two counts share one counter: cx + 65536 cy
-
-template <class Seg> using SegTab = const __attribute__((address_space(4))) Seg*;
-
-// The last segment whose first item is <= it (`first` is strictly increasing, tab[0].first = 0).
-template <class Seg>
-__device__ __forceinline__ int sp_seg_find(SegTab<Seg> tab, int nseg, int64_t it) {
-  int lo = 0, hi = nseg - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].first <= it) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // The fields of segment s the replicate uses (scalar loads: the address is workgroup-uniform).
 template <class Seg>
@@ -276,22 +264,20 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_sign_panel(const SignSegConst* _
   for (uint32_t t = threadIdx.x; t < SP_CAP; t += DCOR_BLOCK) lds.cnt[t] = 0;
   const double mean0 = means[0], mean1 = means[1], mean2 = means[2], mean3 = means[3];
   SignConst c{};
-  int64_t first = 0, end = 0, out_row = 0;   // items [first, end) belong to the loaded segment
+  SegCursor cur;
+  int64_t out_row = 0;
   for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
-    if (it >= end) {   // a workgroup's items ascend: the table is re-read once per segment entered
-      const int s = __builtin_amdgcn_readfirstlane(sp_seg_find(tab, nseg, it));
+    cur.seek(tab, nseg, items, it, [&](int s) {
       sp_seg_load(tab, s, c);
-      first = tab[s].first;
       out_row = tab[s].out_row;
-      end = s + 1 < nseg ? tab[s + 1].first : items;
-    }
-    const uint32_t rep = (uint32_t)c.rep_begin + (uint32_t)(it - first);
+    });
+    const uint32_t rep = (uint32_t)c.rep_begin + (uint32_t)(it - cur.first);
     sign_panel_item(c, rep, mean0, mean1, mean2, mean3,
                     [&](uint32_t g, double2 (&v)[4]) {   // one 64-byte read of the packed pairs
 #pragma unroll
                       for (int q = 0; q < 4; ++q) v[q] = xyc[4 * g + q];
                     },
-                    lds, out + out_row + (it - first));
+                    lds, out + out_row + (it - cur.first));
   }
 }
 
@@ -308,28 +294,26 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_sign_table(const SignPairSegCons
   double mean0 = 0, mean1 = 0, mean2 = 0, mean3 = 0;
   const double4 *xa = nullptr, *yb = nullptr;   // the pair's columns, a flip block per element
   SignConst c{};
-  int64_t first = 0, end = 0, out_row = 0;   // items [first, end) belong to the loaded segment
+  SegCursor cur;
+  int64_t out_row = 0;
   for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
-    if (it >= end) {   // a workgroup's items ascend: the table is re-read once per segment entered
-      const int s = __builtin_amdgcn_readfirstlane(sp_seg_find(tab, nseg, it));
+    cur.seek(tab, nseg, items, it, [&](int s) {
       sp_seg_load(tab, s, c);
-      first = tab[s].first;
       out_row = tab[s].out_row;
-      end = s + 1 < nseg ? tab[s + 1].first : items;
       const int64_t a = tab[s].col_x, b = tab[s].col_y;
       xa = (const double4*)(cols + a * pitch);
       yb = (const double4*)(cols + b * pitch);
       mean0 = means[2 * a]; mean1 = means[2 * a + 1];
       mean2 = means[2 * b]; mean3 = means[2 * b + 1];
-    }
-    const uint32_t rep = (uint32_t)c.rep_begin + (uint32_t)(it - first);
+    });
+    const uint32_t rep = (uint32_t)c.rep_begin + (uint32_t)(it - cur.first);
     sign_panel_item(c, rep, mean0, mean1, mean2, mean3,
                     [&](uint32_t g, double2 (&v)[4]) {   // two 32-byte reads, one per column
                       const double4 x = xa[g], y = yb[g];
                       v[0] = make_double2(x.x, y.x); v[1] = make_double2(x.y, y.y);
                       v[2] = make_double2(x.z, y.z); v[3] = make_double2(x.w, y.w);
                     },
-                    lds, out + out_row + (it - first));
+                    lds, out + out_row + (it - cur.first));
   }
 }
 

@@ -25,13 +25,12 @@
 #include <type_traits>
 
 #include "dcor_common.h"
+#include "dcor_segtab.h"
 
 namespace dcor {
 
 #define SGP_PREP_NT 256
 #define SGP_PREP_MAXGRID 1024
-
-template <class T> using SgpTab = const __attribute__((address_space(4))) T*;
 
 __global__ __launch_bounds__(SGP_PREP_NT) void k_subg_panel_prep(const double* __restrict__ X,
                                                                  const double* __restrict__ Y, int64_t n,
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(SGP_PREP_NT) void k_subg_panel_prep(const double* _
   const int64_t gs = (int64_t)gridDim.x * SGP_PREP_NT;
   for (int64_t i = gt; i < npad; i += gs)   // i >= n: the zero padding of the last pair
     xy[i] = i < n ? make_double2(X[i], Y[i]) : make_double2(0.0, 0.0);
-  const SgpTab<SubgMeanSlot> slots = (SgpTab<SubgMeanSlot>)slots_g;
+  const SegTab<SubgMeanSlot> slots = (SegTab<SubgMeanSlot>)slots_g;
   for (int d = 0; d < nslots; ++d) {
     const int64_t k = slots[d].k, off = slots[d].off;
     const int32_t m = slots[d].m, pow2 = slots[d].md_pow2;
@@ -72,23 +71,13 @@ struct SubgPackedLoad {
 };
 
 // The segment's fields over the call-wide ones in c (scalar loads: the address is uniform).
-__device__ __forceinline__ void sgp_seg_load(SgpTab<SubgSegConst> tab, int s, SubgConst& c) {
+__device__ __forceinline__ void sgp_seg_load(SegTab<SubgSegConst> tab, int s, SubgConst& c) {
   c.k = tab[s].k; c.m = tab[s].m; c.md_pow2 = tab[s].md_pow2; c.sender_is_X = tab[s].sender_is_X;
   c.md = tab[s].md; c.kd = tab[s].kd; c.inv_md = tab[s].inv_md;
   c.bx = tab[s].bx; c.by = tab[s].by; c.m_over_k = tab[s].m_over_k; c.sqrt_k = tab[s].sqrt_k;
   c.ls = tab[s].ls; c.lr = tab[s].lr; c.bs = tab[s].bs; c.s_central = tab[s].s_central;
   c.sn2x2 = tab[s].sn2x2; c.eps_r = tab[s].eps_r;
   c.k0 = tab[s].k0; c.k1 = tab[s].k1; c.rep_begin = tab[s].rep_begin;
-}
-
-// The last segment whose first item is <= it (`first` is strictly increasing, tab[0].first = 0).
-__device__ __forceinline__ int sgp_seg_find(SgpTab<SubgSegConst> tab, int nseg, int64_t it) {
-  int lo = 0, hi = nseg - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].first <= it) lo = mid; else hi = mid - 1;
-  }
-  return lo;
 }
 
 // The LDS of one workgroup: the log table, and the epilogue's of a wave or workgroup replicate.
@@ -175,7 +164,7 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_subg_panel(SubgConst c,
                                                            const double2* __restrict__ means,
                                                            dcor_rep_out* __restrict__ out) {
   __shared__ SgpLds<WAVE, VPL> lds;
-  const SgpTab<SubgSegConst> tab = (SgpTab<SubgSegConst>)tab_g;
+  const SegTab<SubgSegConst> tab = (SegTab<SubgSegConst>)tab_g;
   log_tab_to_lds(lds.lt, DCOR_BLOCK);
   __syncthreads();
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -183,20 +172,18 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_subg_panel(SubgConst c,
   const int64_t units = WAVE ? (int64_t)gridDim.x * DCOR_WAVES : (int64_t)gridDim.x;
   const SubgPackedLoad load{xy};
   const double2* bm = means;
-  int64_t first = 0, end = 0, out_row = 0;   // items [first, end) belong to the loaded segment
+  SegCursor cur;
+  int64_t out_row = 0;
   for (int64_t it = unit; it < items; it += units) {
-    if (it >= end) {
-      const int s = __builtin_amdgcn_readfirstlane(sgp_seg_find(tab, nseg, it));
+    cur.seek(tab, nseg, items, it, [&](int s) {
       sgp_seg_load(tab, s, c);
       bm = means + tab[s].mean_off;
-      first = tab[s].first;
       out_row = tab[s].out_row;
-      end = s + 1 < nseg ? tab[s + 1].first : items;
-    }
+    });
     // the previous item's readers of the epilogue's LDS are done
     if constexpr (WAVE) wave_sync(); else __syncthreads();
-    const uint32_t rep = (uint32_t)c.rep_begin + (uint32_t)(it - first);
-    subg_panel_item<WAVE, VPL>(c, rep, load, bm, lds.lt, lds, out + out_row + (it - first));
+    const uint32_t rep = (uint32_t)c.rep_begin + (uint32_t)(it - cur.first);
+    subg_panel_item<WAVE, VPL>(c, rep, load, bm, lds.lt, lds, out + out_row + (it - cur.first));
   }
 }
 

@@ -225,6 +225,31 @@ def segment_shard(seg_reps, rank: int, world: int):
     return out
 
 
+def shard_segments(segs, i_rep_begin: int, i_reps: int, rank: int, world: int):
+    """Rank `rank`'s pieces of segs, whose tuples hold rep_begin at i_rep_begin and reps at i_reps:
+    for every piece of segment_shard the segment's tuple with rep_begin moved on by the piece's
+    offset and reps the piece's count, every other field kept."""
+    def piece(seg, r0, c):
+        seg = list(seg)
+        seg[i_rep_begin], seg[i_reps] = int(seg[i_rep_begin]) + r0, c
+        return tuple(seg)
+    return [piece(segs[j], r0, c) for j, r0, c in segment_shard([int(s[i_reps]) for s in segs], rank, world)]
+
+
+def _segments_distributed(run, segs, i_rep_begin, i_reps, group):
+    """run(pieces) -> [count, 6] on this rank's shard_segments pieces, the ranks' records
+    all-gathered in rank order."""
+    import torch.distributed as dist
+    segs = list(segs)
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    total = sum(int(s[i_reps]) for s in segs)
+    if total == 0:   # the same on every rank: nothing to run or gather
+        return np.zeros((0, 6))
+    mine = shard_segments(segs, i_rep_begin, i_reps, rank, world)
+    local = run(mine) if mine else np.zeros((0, 6))
+    return gather_rows(local, [shard(total, r, world)[1] for r in range(world)], group)
+
+
 def sign_table_distributed(D, segs, group=None, **kw):
     """dcor.signpanel.table_segments over G ranks: the flattened (segment, replicate) space of segs
     [(col_x, col_y, eps1, eps2, seed, rep_begin, reps), ...] is split into contiguous per-rank
@@ -232,18 +257,8 @@ def sign_table_distributed(D, segs, group=None, **kw):
     moved on by the piece's offset -- in one native call, and the records are all-gathered in rank
     order.  A record depends only on (columns, eps1, eps2, seed, replicate), so the [sum(reps), 6]
     result, identical on all ranks, equals one process's table_segments(D, segs) byte for byte."""
-    import torch.distributed as dist
-
     from . import signpanel
-    segs = list(segs)
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    seg_reps = [int(s[6]) for s in segs]
-    if sum(seg_reps) == 0:   # the same on every rank: nothing to run or gather
-        return np.zeros((0, 6))
-    mine = [(*segs[j][:5], int(segs[j][5]) + r0, c) for j, r0, c in segment_shard(seg_reps, rank, world)]
-    local = signpanel.table_segments(D, mine, **kw) if mine else np.zeros((0, 6))
-    counts = [shard(sum(seg_reps), r, world)[1] for r in range(world)]
-    return gather_rows(local, counts, group)
+    return _segments_distributed(lambda mine: signpanel.table_segments(D, mine, **kw), segs, 5, 6, group)
 
 
 def subg_panel_distributed(X, Y, segs, group=None, **kw):
@@ -254,18 +269,8 @@ def subg_panel_distributed(X, Y, segs, group=None, **kw):
     in rank order.  A record depends only on (panel, eta, eps1, eps2, seed, replicate), so the
     [sum(reps), 6] result, identical on all ranks, equals one process's sweep_segments(X, Y, segs)
     byte for byte."""
-    import torch.distributed as dist
-
     from . import subgpanel
-    segs = list(segs)
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    seg_reps = [int(s[4]) for s in segs]
-    if sum(seg_reps) == 0:   # the same on every rank: nothing to run or gather
-        return np.zeros((0, 6))
-    mine = [(*segs[j][:3], int(segs[j][3]) + r0, c) for j, r0, c in segment_shard(seg_reps, rank, world)]
-    local = subgpanel.sweep_segments(X, Y, mine, **kw) if mine else np.zeros((0, 6))
-    counts = [shard(sum(seg_reps), r, world)[1] for r in range(world)]
-    return gather_rows(local, counts, group)
+    return _segments_distributed(lambda mine: subgpanel.sweep_segments(X, Y, mine, **kw), segs, 3, 4, group)
 
 
 def hrs_table_distributed(Z, lam, segs, group=None, **kw):
@@ -276,15 +281,5 @@ def hrs_table_distributed(Z, lam, segs, group=None, **kw):
     all-gathered in rank order.  A record depends only on (columns, lam, eps, seeds, replicate), so
     the [sum(reps), 6] result, identical on all ranks, equals one process's table_segments(Z, lam,
     segs) byte for byte."""
-    import torch.distributed as dist
-
     from . import hrs
-    segs = list(segs)
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    seg_reps = [int(s[6]) for s in segs]
-    if sum(seg_reps) == 0:   # the same on every rank: nothing to run or gather
-        return np.zeros((0, 6))
-    mine = [(*segs[j][:5], int(segs[j][5]) + r0, c) for j, r0, c in segment_shard(seg_reps, rank, world)]
-    local = hrs.table_segments(Z, lam, mine, **kw) if mine else np.zeros((0, 6))
-    counts = [shard(sum(seg_reps), r, world)[1] for r in range(world)]
-    return gather_rows(local, counts, group)
+    return _segments_distributed(lambda mine: hrs.table_segments(Z, lam, mine, **kw), segs, 5, 6, group)

@@ -405,6 +405,7 @@ def table_segments(Z, lam, segs, nsim=2000, alpha=0.05, delta=None, stream=None)
     import ctypes as C
 
     from . import _lib
+    from ._segcall import pack_segments, run_segment_call
     from .signpanel import _table
     segs = list(segs)
     F, n, p = _table(Z)
@@ -414,24 +415,13 @@ def table_segments(Z, lam, segs, nsim=2000, alpha=0.05, delta=None, stream=None)
     for a, b, *_ in segs:
         if not (0 <= int(a) < p and 0 <= int(b) < p):
             raise ValueError(f"columns ({a}, {b}) outside [0, {p})")
-    rows = np.cumsum([0] + [int(s[6]) for s in segs])
-    total = int(rows[-1])
-    arr = (_lib.HrsPairSegment * max(len(segs), 1))(*[
-        _lib.HrsPairSegment(eps=float(e), seed_ni=int(sn), seed_int=int(si), rep_begin=int(rb), reps=int(c),
-                            out_row=int(rows[j]), col_x=int(a), col_y=int(b))
-        for j, (a, b, e, sn, si, rb, c) in enumerate(segs)])
+    arr, total = pack_segments(_lib.HrsPairSegment, segs, 6)
     import torch
     Dd = torch.as_tensor(F.reshape(-1, order="F"), device="cuda")   # the one upload
-    st = torch.cuda.current_stream() if stream is None else stream
-    out = torch.empty((max(total, 1), 6), dtype=torch.float64, device="cuda")
     desc = _lib.HrsTableDesc(n=n, p=p, ld=n, D=Dd.data_ptr(), lam=lam.ctypes.data_as(C.POINTER(C.c_double)),
                              alpha=float(alpha), delta=1.0 / n if delta is None else float(delta),
                              nsim=int(nsim))
-    with torch.cuda.stream(st):
-        _lib.check(_lib.lib.dcor_hrs_table_launch(C.byref(desc), arr, len(segs),
-                                                  C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
-        res = out[:total].cpu().numpy()   # waits for the stream: the table outlives the call's work
-    return res
+    return run_segment_call(_lib.lib.dcor_hrs_table_launch, desc, arr, len(segs), total, stream)
 
 
 def corr_matrix(Z, lam, eps, reps, pairs=None, nsim=2000, alpha=0.05, delta=None, stream=None):

@@ -15,41 +15,24 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-
-
-def _segments(segs):
-    """[(eps1, eps2, seed, rep_begin, reps), ...] -> (ctypes array, rows, total): records in
-    segment order."""
-    rows = np.cumsum([0] + [int(s[4]) for s in segs])
-    arr = (_lib.SignSegment * max(len(segs), 1))(*[
-        _lib.SignSegment(eps1=float(e1), eps2=float(e2), seed=int(seed), rep_begin=int(rb), reps=int(c),
-                         out_row=int(rows[j]))
-        for j, (e1, e2, seed, rb, c) in enumerate(segs)])
-    return arr, rows, int(rows[-1])
+from ._segcall import pack_segments, run_segment_call
 
 
 def sweep_segments(X, Y, segs, alpha=0.05, normalise=True, mode="auto", nsim=1000, stream=None):
     """The replicates of several (eps1, eps2, seed, rep_begin, reps) segments on one shared panel
     in one native call -> float64 [sum(reps), 6] (ni_hat, ni_lo, ni_hi, int_hat, int_lo, int_hi) in
     segment order.  Each segment's records equal `replicates` with the same arguments bit for bit."""
-    import ctypes as C
-
     ci_mode = _lib.mode_code(mode)
-    arr, _, total = _segments(list(segs))
+    segs = list(segs)
+    arr, total = pack_segments(_lib.SignSegment, segs, 4)
     import torch
     Xd = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float64), device="cuda")
     Yd = torch.as_tensor(np.ascontiguousarray(Y, dtype=np.float64), device="cuda")
     if Xd.ndim != 1 or Xd.shape != Yd.shape:
         raise ValueError("X and Y must be vectors of one length")
-    st = torch.cuda.current_stream() if stream is None else stream
-    out = torch.empty((max(total, 1), 6), dtype=torch.float64, device="cuda")
     desc = _lib.SignPanelDesc(n=int(Xd.shape[0]), X=Xd.data_ptr(), Y=Yd.data_ptr(), alpha=float(alpha),
                               normalise=1 if normalise else 0, ci_mode=ci_mode, nsim=int(nsim))
-    with torch.cuda.stream(st):
-        _lib.check(_lib.lib.dcor_sign_panel_launch(C.byref(desc), arr, len(segs),
-                                                   C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
-        res = out[:total].cpu().numpy()   # waits for the stream: X, Y outlive the call's work
-    return res
+    return run_segment_call(_lib.lib.dcor_sign_panel_launch, desc, arr, len(segs), total, stream)
 
 
 def replicates(X, Y, eps1, eps2, reps, seed, rep_begin=0, alpha=0.05, normalise=True, mode="auto",
@@ -89,31 +72,18 @@ def table_segments(D, segs, alpha=0.05, normalise=True, mode="auto", nsim=1000, 
     [sum(reps), 6] in segment order.  Each segment's records equal `replicates(D[:, col_x],
     D[:, col_y], eps1, eps2, reps, seed, rep_begin)` bit for bit; X (col_x) is the sender side as
     there, so (a, b) and (b, a) are different segments."""
-    import ctypes as C
-
     ci_mode = _lib.mode_code(mode)
     segs = list(segs)
     F, n, p = _table(D)
     for a, b, *_ in segs:
         if not (0 <= int(a) < p and 0 <= int(b) < p):
             raise ValueError(f"columns ({a}, {b}) outside [0, {p})")
-    rows = np.cumsum([0] + [int(s[6]) for s in segs])
-    total = int(rows[-1])
-    arr = (_lib.SignPairSegment * max(len(segs), 1))(*[
-        _lib.SignPairSegment(eps1=float(e1), eps2=float(e2), seed=int(seed), rep_begin=int(rb), reps=int(c),
-                             out_row=int(rows[j]), col_x=int(a), col_y=int(b))
-        for j, (a, b, e1, e2, seed, rb, c) in enumerate(segs)])
+    arr, total = pack_segments(_lib.SignPairSegment, segs, 6)
     import torch
     Dd = torch.as_tensor(F.reshape(-1, order="F"), device="cuda")   # the one upload
-    st = torch.cuda.current_stream() if stream is None else stream
-    out = torch.empty((max(total, 1), 6), dtype=torch.float64, device="cuda")
     desc = _lib.SignTableDesc(n=n, p=p, ld=n, D=Dd.data_ptr(), alpha=float(alpha),
                               normalise=1 if normalise else 0, ci_mode=ci_mode, nsim=int(nsim))
-    with torch.cuda.stream(st):
-        _lib.check(_lib.lib.dcor_sign_table_launch(C.byref(desc), arr, len(segs),
-                                                   C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
-        res = out[:total].cpu().numpy()   # waits for the stream: the table outlives the call's work
-    return res
+    return run_segment_call(_lib.lib.dcor_sign_table_launch, desc, arr, len(segs), total, stream)
 
 
 def all_pairs(p):

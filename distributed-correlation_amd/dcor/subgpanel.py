@@ -12,41 +12,23 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-
-
-def _segments(segs):
-    """[(eps1, eps2, seed, rep_begin, reps), ...] -> (ctypes array, total): records in segment
-    order."""
-    rows = np.cumsum([0] + [int(s[4]) for s in segs])
-    arr = (_lib.SubgSegment * max(len(segs), 1))(*[
-        _lib.SubgSegment(eps1=float(e1), eps2=float(e2), seed=int(seed), rep_begin=int(rb), reps=int(c),
-                         out_row=int(rows[j]))
-        for j, (e1, e2, seed, rb, c) in enumerate(segs)])
-    return arr, int(rows[-1])
+from ._segcall import pack_segments, run_segment_call
 
 
 def sweep_segments(X, Y, segs, eta1=1.0, eta2=1.0, alpha=0.05, nsim=1000, stream=None):
     """The replicates of several (eps1, eps2, seed, rep_begin, reps) segments on one shared panel
     in one native call -> float64 [sum(reps), 6] (ni_hat, ni_lo, ni_hi, int_hat, int_lo, int_hi) in
     segment order.  Each segment's records equal `replicates` with the same arguments bit for bit."""
-    import ctypes as C
-
     segs = list(segs)
-    arr, total = _segments(segs)
+    arr, total = pack_segments(_lib.SubgSegment, segs, 4)
     import torch
     Xd = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float64), device="cuda")
     Yd = torch.as_tensor(np.ascontiguousarray(Y, dtype=np.float64), device="cuda")
     if Xd.ndim != 1 or Xd.shape != Yd.shape:
         raise ValueError("X and Y must be vectors of one length")
-    st = torch.cuda.current_stream() if stream is None else stream
-    out = torch.empty((max(total, 1), 6), dtype=torch.float64, device="cuda")
     desc = _lib.SubgPanelDesc(n=int(Xd.shape[0]), X=Xd.data_ptr(), Y=Yd.data_ptr(), eta1=float(eta1),
                               eta2=float(eta2), alpha=float(alpha), nsim=int(nsim))
-    with torch.cuda.stream(st):
-        _lib.check(_lib.lib.dcor_subg_panel_launch(C.byref(desc), arr, len(segs),
-                                                   C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
-        res = out[:total].cpu().numpy()   # waits for the stream: X, Y outlive the call's work
-    return res
+    return run_segment_call(_lib.lib.dcor_subg_panel_launch, desc, arr, len(segs), total, stream)
 
 
 def replicates(X, Y, eps1, eps2, reps, seed, rep_begin=0, eta1=1.0, eta2=1.0, alpha=0.05, nsim=1000,
