@@ -24,6 +24,7 @@ namespace dcor {
 // ------------------------------------------------------------------ Philox
 struct U4 { uint32_t w0, w1, w2, w3; };
 
+#define DCOR_PHILOX_M0 0xD2511F53u
 // a ^ b ^ k in one gfx950 v_bitop3_b32 (truth table 0x96).  The builtin, not inline asm: the
 // compiler does not form bitop3 from a ^ b ^ k by itself, and after an asm statement it pads with
 // a hazard s_nop (7.5 per pass-1 sample).
@@ -31,19 +32,26 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t k) {
   return __builtin_amdgcn_bitop3_b32(a, b, k, 0x96);
 }
 
-__device__ __forceinline__ U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                     uint32_t k0, uint32_t k1) {
+// Rounds 2-10 follow round 1 from its first product p0 = 0xD2511F53 * c0 (64 bits), which a caller
+// with several counters c0 = v + const may form as one multiply-add: 0xD2511F53 * v + 0xD2511F53 * const.
+__device__ __forceinline__ U4 philox_p0(uint64_t p0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                        uint32_t k0, uint32_t k1) {
   // 32x32->64 products map to one v_mad_u64_u32 each (hi and lo together); the two
   // xors of each output word are one v_bitop3_b32.
+  uint32_t c0 = 0;
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+    if (r > 0) p0 = (uint64_t)DCOR_PHILOX_M0 * c0;
     const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
     const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0), n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
     c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
   return U4{c0, c1, c2, c3};
+}
+__device__ __forceinline__ U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                     uint32_t k0, uint32_t k1) {
+  return philox_p0((uint64_t)DCOR_PHILOX_M0 * c0, c1, c2, c3, k0, k1);
 }
 
 __device__ __forceinline__ U4 draw(uint32_t idx, uint32_t rep, uint32_t site, uint32_t k0,
@@ -170,6 +178,22 @@ __device__ __forceinline__ uint32_t zig_y1(uint32_t w2) { return (w2 << 27) | 0x
 __device__ __forceinline__ uint32_t zig_y2(uint32_t w2) { return ((w2 << 11) & 0xf8000000u) | 0x4000000u; }
 __device__ __forceinline__ uint32_t zig_j1(uint32_t w2) { return (w2 >> 5) & 2047u; }
 __device__ __forceinline__ uint32_t zig_j2(uint32_t w2) { return w2 >> 21; }
+// The byte offsets 16 j1, 16 j2 of a sample's two layer-table entries from t = w2 >> 1 (one shift
+// shared by both), and zig_y2 from a mask and one v_lshl_or_b32 (`m5` = 0x1f0000, held in a
+// register by the caller: with a literal the compiler shifts first and then needs an and and an or).
+__device__ __forceinline__ uint32_t zig_o1(uint32_t t) { return t & 0x7ff0u; }
+__device__ __forceinline__ uint32_t zig_o2(uint32_t t) { return (t >> 16) & 0x7ff0u; }
+__device__ __forceinline__ uint32_t zig_y2m(uint32_t w2, uint32_t m5) { return ((w2 & m5) << 11) | 0x4000000u; }
+
+// acc << 1 | (lane's bit of the lane mask m) in one v_addc_co_u32 (acc + acc + carry-in): a compare's
+// lane mask, combined with others on the scalar side, enters a lane's bit register without a
+// v_cndmask and an or.  Not volatile, so the scheduler places it like any other VALU instruction.
+__device__ __forceinline__ uint32_t shl1_in(uint32_t acc, uint64_t m) {
+  uint32_t r;
+  uint64_t co;
+  asm("v_addc_co_u32_e64 %0, %1, %2, %2, %3" : "=v"(r), "=s"(co) : "v"(acc), "s"(m));
+  return r;
+}
 
 // The full draw from attempt 0's (A, H): fast test, then the wedge test (L >= 1) against
 // f(x) = exp(-x^2/2) compared in logs, or the base layer's tail (L = 0: Marsaglia's x = -log(U1)/r,

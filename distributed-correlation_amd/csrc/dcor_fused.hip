@@ -234,9 +234,13 @@ __device__ __forceinline__ uint32_t rec_of(uint32_t P, uint32_t fl) {
   return ((P >> 9) & 0x7fu) | ((P >> 17) & 0x7f00u) | fl;
 }
 // two records in one word: sample a in the low half
-__device__ __forceinline__ uint32_t rec_pair(uint32_t Pa, uint32_t Pb, uint32_t fla, uint32_t flb) {
+// fa: sample a's flip as 0 or 0x80; fb16: sample b's already in the high half, 0 or 0x800000
+__device__ __forceinline__ uint32_t rec_pair_placed(uint32_t Pa, uint32_t Pb, uint32_t fa, uint32_t fb16) {
   const uint32_t hb = __builtin_amdgcn_perm(Pb, Pa, 0x07050301u);   // high bytes: xa, ya, xb, yb
-  return ((hb >> 1) & 0x7f7f7f7fu) | fla | (flb << 16);
+  return ((hb >> 1) & 0x7f7f7f7fu) | fa | fb16;
+}
+__device__ __forceinline__ uint32_t rec_pair(uint32_t Pa, uint32_t Pb, uint32_t fla, uint32_t flb) {
+  return rec_pair_placed(Pa, Pb, fla, flb << 16);
 }
 
 template <int DGP>
@@ -511,21 +515,83 @@ __device__ __forceinline__ void sign_pass1_core(const SignConst& c, uint32_t rep
           if (cnt >= 64u) flush(64u);
         }
       };
+      // `acc` holds a step's byte bit-reversed (the step's sample s = 4 h + j at bit 7 - s), because
+      // the steady trips shift one bit per sample in from the right; quad_word puts the bits of
+      // each byte back in take()'s order.
       auto quad_word = [&](uint32_t word) {
+        word = __builtin_bswap32(__builtin_bitreverse32(word));
         if constexpr (CEIL == 1 || CEIL == 2)
           asm volatile("" ::"v"(word));
         else
           take(word, 64 * (int64_t)wv + (int64_t)(2 * NT) * (4 * (int64_t)q), false);
         ++q;
       };
-      for (int64_t b = 64 * wv; b < nfull; b += 2 * NT) {  // trip count uniform per wave
+      // The steady trip's group (every lane has it: no guard, no validity select): samples
+      // iv + 4 NT H + (0 .. 3), iv = 4 (b + lane).  The same operations on a sample as group()'s, in
+      // the same order; what differs is the integer glue.
+      // - The Philox counter's first product takes the sample's offset from iv in its addend.
+      // - The two fast-path compares of a sample stay lane masks: one scalar or, and one
+      //   v_addc_co_u32 shifts the sample's pend bit into `acc`.
+      // - The slab store takes the scalar slab base, the 32-bit byte offset 2 iv and an immediate.
+      // Needs flipT != 0, so that the flip is the constant bit 7 under one compare.
+      uint32_t m5 = 0x1f0000u;
+      asm("" : "+s"(m5));   // a register, not a literal (zig_y2m)
+      auto group_fast = [&](uint32_t iv, auto h_tag, double& hx, double& hy) {
+        constexpr uint32_t H = decltype(h_tag)::value;
+        uint32_t P[4], fa[4];
+        double gx, gy;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint64_t p0 = (uint64_t)DCOR_PHILOX_M0 * iv + (uint64_t)DCOR_PHILOX_M0 * (uint64_t)(4u * NT * H + (uint32_t)j);
+          const U4 w = philox_p0(p0, rep, DCOR_SITE_DGP_A, 0u, c.k0, c.k1);
+          const uint32_t t = w.w2 >> 1;
+          const double2 t1 = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(zt) + zig_o1(t));
+          const double2 t2 = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(zt) + zig_o2(t));
+          const double z1 = fma(zig_d(w.w0, zig_y1(w.w2)), t1.x, -t1.x);
+          const double z2 = fma(zig_d(w.w1, zig_y2m(w.w2, m5)), t2.x, -t2.x);
+          acc = shl1_in(acc, __ballot(!(fabs(z1) < t1.y)) | __ballot(!(fabs(z2) < t2.y)));
+          double x, y;
+          mvn_z(z1, z2, c.g.mu0, c.g.mu1, c.g.a00, c.g.a01, c.g.a10, c.g.a11, &x, &y);
+          const double xc = rclip_fin(x, c.L), yc = rclip_fin(y, c.L);
+          gx = j == 0 ? xc : gx + xc;
+          gy = j == 0 ? yc : gy + yc;
+          P[j] = code16_pair(xc, yc, cix, ciy, cbx, cby);
+          fa[j] = w.w3 <= ftm1 ? ((j & 1) ? 0x800000u : 0x80u) : 0u;
+        }
+        hx += gx;
+        hy += gy;
+        const uint32_t r01 = rec_pair_placed(P[0], P[1], fa[0], fa[1]), r23 = rec_pair_placed(P[2], P[3], fa[2], fa[3]);
+        if constexpr (CEIL == 1 || CEIL == 3)
+          asm volatile("" ::"v"(r01), "v"(r23));
+        else
+          *reinterpret_cast<uint2*>(reinterpret_cast<char*>(slab) + (uint64_t)(2u * iv) + 8u * NT * H) = make_uint2(r01, r23);
+      };
+      // Steady trips: both groups of every lane of the wave lie below nfull (a scalar test); then
+      // at most one guarded trip.  Sample and group indices are 32-bit (check_common: n < 2^31).
+      const uint32_t nf = (uint32_t)nfull;
+      uint32_t b = 64u * (uint32_t)__builtin_amdgcn_readfirstlane(wv);
+      if (c.flipT != 0) {
+        for (uint32_t iv = 4u * (b + (uint32_t)lane); b + 2u * NT <= nf; b += 2u * NT, iv += 8u * NT) {
+          double hx = 0.0, hy = 0.0;
+          group_fast(iv, std::integral_constant<uint32_t, 0>(), hx, hy);
+          group_fast(iv, std::integral_constant<uint32_t, 1>(), hx, hy);
+          ks_acc(sx, hx);
+          ks_acc(sy, hy);
+          if (++s4 == 4) {
+            quad_word(acc);
+            acc = 0;
+            s4 = 0;
+          }
+        }
+      }
+      for (; b < nf; b += 2 * NT) {  // guarded (flipT == 0: every trip); trip count uniform per wave
         double hx = 0.0, hy = 0.0;
         uint32_t pa = 0, pb = 0;
-        if (b + lane < nfull) group(b + lane, std::true_type(), hx, hy, pa);
-        if (b + NT + lane < nfull) group(b + NT + lane, std::true_type(), hx, hy, pb);
+        if (b + lane < nf) group(b + lane, std::true_type(), hx, hy, pa);
+        if (b + NT + lane < nf) group(b + NT + lane, std::true_type(), hx, hy, pb);
         ks_acc(sx, hx);
         ks_acc(sy, hy);
-        acc = (acc << 8) | pa | (pb << 4);
+        acc = (acc << 8) | (__builtin_bitreverse32(pa | (pb << 4)) >> 24);
         if (++s4 == 4) {
           quad_word(acc);
           acc = 0;
