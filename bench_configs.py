@@ -568,6 +568,56 @@ def sign_table(R, p=8, arm="both"):
         print(json.dumps({"config": "ST-check", "records_bit_equal": same}), flush=True)
 
 
+def subg_table(R, p=8, arm="both"):
+    """SGT: the simulation's sub-G estimators on every column pair of a p-column stand-in table
+    (n = 19,433): the p (p - 1) / 2 pairs x 23 eps x R sweep in one dcor_subg_table_launch call
+    (SGT), and the same work -- same table, eps grid, keys and R -- as one subgpanel.sweep_segments
+    call per pair (SGT-per-pair), the only route before the table entry.  arm: "table", "pairs" or
+    "both".  Not in the default list: reach it with --only SGT (--only SGT-table / SGT-pairs for one
+    arm)."""
+    import numpy as np
+    import torch
+    from dcor import hrs, signpanel, subgpanel
+    D = signpanel.standin_table(19433, p, 0.3)
+    pairs = signpanel.all_pairs(p)
+    ne = len(hrs.EPS_GRID)
+    seed = 1_000_000
+
+    def table():   # corr_matrix_sweep's segments and keys, without its host-side summaries
+        segs = [(a, b, e, e, seed + j * ne + idx, 0, R) for j, (a, b) in enumerate(pairs)
+                for idx, e in enumerate(hrs.EPS_GRID, start=1)]
+        return subgpanel.table_segments(D, segs).reshape(len(pairs), ne, R, 6)
+
+    def per_pair():
+        cols = [np.ascontiguousarray(D[:, c]) for c in range(p)]
+        return np.stack([subgpanel.sweep_segments(cols[a], cols[b], [(e, e, seed + j * ne + idx, 0, R)
+                                                                      for idx, e in enumerate(hrs.EPS_GRID, start=1)])
+                         for j, (a, b) in enumerate(pairs)]).reshape(len(pairs), ne, R, 6)
+
+    total = len(pairs) * ne * R
+    res = {}
+    for name, fn, kernel, note in (
+            ("SGT", table, "k_subg_table_prep + k_subg_table",
+             "host wall time of one call: table upload, one preparation launch over the columns, one replicate "
+             "launch over every (pair, eps) segment, records copied back"),
+            ("SGT-per-pair", per_pair, "k_subg_panel_prep + k_subg_panel",
+             "host wall time of one sweep_segments call per pair: two uploads, a preparation launch, a "
+             "replicate launch over the pair's 23 eps and a D2H wait each")):
+        if arm != "both" and (arm == "table") != (name == "SGT"):
+            continue
+        fn()    # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res[name] = fn()
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        line(name, n=int(D.shape[0]), p=p, pairs=len(pairs), replicates=total, seconds=t, reps_per_s=total / t,
+             finite=bool(np.isfinite(res[name][..., [0, 3, 4, 5]]).all()), kernel=kernel, note=note)
+    if len(res) == 2:
+        same = bool(np.array_equal(res["SGT"].view(np.uint64), res["SGT-per-pair"].view(np.uint64)))
+        print(json.dumps({"config": "SGT-check", "records_bit_equal": same}), flush=True)
+
+
 def hrs_table(R, p=8, arm="both"):
     """HT: the HRS estimators on every column pair of a p-column stand-in table (n = 19,433) with a
     clip bound per column: the p (p - 1) / 2 pairs x 23 eps x R sweep in one dcor_hrs_table_launch
@@ -929,6 +979,9 @@ def main():
     if "ST" in which: sign_table(a.hs_R)
     if "ST-table" in which: sign_table(a.hs_R, arm="table")
     if "ST-pairs" in which: sign_table(a.hs_R, arm="pairs")
+    if "SGT" in which: subg_table(a.hs_R)
+    if "SGT-table" in which: subg_table(a.hs_R, arm="table")
+    if "SGT-pairs" in which: subg_table(a.hs_R, arm="pairs")
     if "HT" in which: hrs_table(a.hs_R)
     if "HT-table" in which: hrs_table(a.hs_R, arm="table")
     if "HT-pairs" in which: hrs_table(a.hs_R, arm="pairs")

@@ -1170,6 +1170,28 @@ int dcor_subg_panel_launch(const dcor_subg_panel_desc* p, const dcor_subg_segmen
   }, false, {{lay.slot_off, slots.data(), slots.size() * sizeof(SubgMeanSlot)}});
 }
 
+int dcor_subg_table_launch(const dcor_subg_table_desc* t, const dcor_subg_pair_segment* segs,
+                           int64_t nseg, dcor_rep_out* d_out, void* stream) {
+  if (int st = seg_args("subg_table", t, segs, nseg, d_out)) return st;
+  if (nseg == 0) return DCOR_OK;   // nothing to run
+  std::vector<SubgPairSegConst> tab;
+  std::vector<SubgMeanSlot> slots;
+  std::vector<double> clips;
+  SubgConst c0;
+  int64_t items = 0;
+  if (int st = plan_subg_table(t, segs, nseg, tab, slots, clips, &c0, &items)) return st;
+  if (items == 0) return DCOR_OK;
+  if (int st = need_device()) return st;
+  const int64_t nmeans = slots.back().off + slots.back().k;
+  const SubgTableLayout lay((int64_t)tab.size(), (int64_t)slots.size(), nmeans, t->n, t->p);
+  return with_table("subg_table", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
+    return launch_subg_table(c0, t->D, t->p, t->ld, lay.clips(buf), lay.slots(buf), (int)slots.size(),
+                             lay.means(buf), lay.mpitch, lay.cols(buf), lay.npad, lay.tab(buf), (int)tab.size(),
+                             items, d_out, stream);
+  }, false, {{lay.slot_off, slots.data(), slots.size() * sizeof(SubgMeanSlot)},
+             {lay.clip_off, clips.data(), clips.size() * sizeof(double)}});
+}
+
 int dcor_panel_dict_probe(const double* d_X, const double* d_Y, int64_t n, int* ok) {
   if (!d_X || !d_Y || !ok || n < 1) return fail(DCOR_EINVAL, "panel_dict_probe: bad arguments");
   if (int st = need_device()) return st;

@@ -445,6 +445,57 @@ int launch_subg_panel(const SubgConst& c, const double* X, const double* Y, cons
                       int nslots, double2* means, double2* xy, int64_t npad, const SubgSegConst* tab,
                       int nseg, int64_t items, dcor_rep_out* out, void* stream);
 
+// ---- sub-G simulation estimators on the column pairs of a shared table (dcor_subg_table_launch) ----
+// A sub-G panel segment and the two columns it reads: X = column col_x, Y = column col_y.  With an
+// eta per column nothing that depends on eta is call-wide: ls, lr and bs are the record's already
+// and the NI clips are applied by the preparation launch, so the kernel argument SubgConst carries
+// only n, nd, sqrt_n, crit and mix.
+struct SubgPairSegConst : SubgSegConst {
+  int32_t col_x, col_y;
+};
+static_assert(sizeof(SubgPairSegConst) == 176, "the sub-G table's device table stride");
+// Sub-G table scratch: the segment table | the slot table | the p NI clips lambda_n(n, eta[c]) |
+// the batch means, per column a row of every slot's k means (doubles, [p][nmeans] at pitch mpitch =
+// nmeans rounded up to 2, so each row starts 16-B aligned; a slot's means start at its off) | the p
+// columns as plain doubles, each zero-padded to npad = n rounded up to 4, so every column starts
+// 32-B aligned.  Every region starts 256-B aligned when the base is.  ok is false when a region's
+// bytes (or the total) are not representable.
+struct SubgTableLayout {
+  int64_t npad, mpitch;
+  size_t tab_off = 0, slot_off = 0, clip_off = 0, means_off = 0, cols_off = 0, bytes = 0;
+  bool ok = false;
+  SubgTableLayout(int64_t nseg, int64_t nslots, int64_t nmeans, int64_t n, int64_t p)
+      : npad((n + 3) & ~(int64_t)3), mpitch((nmeans + 1) & ~(int64_t)1) {
+    const size_t lim = SIZE_MAX / 2;
+    if (n < 1 || p < 1 || nseg < 0 || nslots < 0 || nmeans < 0 || (size_t)p > lim / 16 ||
+        (size_t)nseg > lim / (2 * sizeof(SubgPairSegConst)) || (size_t)nslots > lim / (4 * sizeof(SubgMeanSlot)) ||
+        (size_t)nmeans > lim / 16)
+      return;
+    slot_off = al256((size_t)nseg * sizeof(SubgPairSegConst));
+    clip_off = slot_off + al256((size_t)nslots * sizeof(SubgMeanSlot));
+    means_off = clip_off + al256((size_t)p * sizeof(double));
+    const size_t row_bytes = (size_t)mpitch * sizeof(double), col_bytes = (size_t)npad * sizeof(double);
+    if (means_off > lim || (row_bytes && (size_t)p > (lim - means_off) / row_bytes)) return;
+    cols_off = means_off + al256((size_t)p * row_bytes);
+    if (cols_off > lim || (size_t)p > (lim - cols_off) / col_bytes) return;
+    bytes = cols_off + (size_t)p * col_bytes;
+    ok = true;
+  }
+  SubgPairSegConst* tab(void* base) const { return (SubgPairSegConst*)((char*)base + tab_off); }
+  SubgMeanSlot* slots(void* base) const { return (SubgMeanSlot*)((char*)base + slot_off); }
+  double* clips(void* base) const { return (double*)((char*)base + clip_off); }
+  double* means(void* base) const { return (double*)((char*)base + means_off); }
+  double* cols(void* base) const { return (double*)((char*)base + cols_off); }
+};
+// The preparation launch (every column of D copied to pitch npad, and every (column, slot)'s batch
+// means of the column clipped at clips[c]: k_subg_panel_prep's arithmetic, one writer per value) and
+// the replicate launch over `items` replicates of the nseg >= 1 segments in `tab` (device), as
+// launch_subg_panel.  c: n, nd, sqrt_n, crit and mix; clips, slots: device.
+int launch_subg_table(const SubgConst& c, const double* D, int64_t p, int64_t ld, const double* clips,
+                      const SubgMeanSlot* slots, int nslots, double* means, int64_t mpitch, double* cols,
+                      int64_t npad, const SubgPairSegConst* tab, int nseg, int64_t items, dcor_rep_out* out,
+                      void* stream);
+
 // ---- sign family on a shared panel (dcor_sign_panel_launch; dcor_signpanel.hip) ----
 // One segment of a sign-panel call: make_sign's constants for the segment's (eps1, eps2) with its
 // Philox key in s.k0 / s.k1 and its first replicate in s.rep_begin, and its place in the call.

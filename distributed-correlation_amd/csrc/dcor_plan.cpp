@@ -1,6 +1,6 @@
 // dcor_plan.cpp -- the device-free half of the host side (dcor_plan.h): the error reporter, the
 // argument checks of the reference's stopifnot() calls, every data-independent scalar of the
-// estimators (R operation order, cited), and the segment planners of the six segment-list
+// estimators (R operation order, cited), and the segment planners of the seven segment-list
 // entries.  No HIP: this file and the headers it includes compile with a host compiler alone.
 #include "dcor_plan.h"
 
@@ -227,7 +227,11 @@ bool eps_ok(const dcor_subg_segment& g) {
 template <class Seg> const char* eps_names(const Seg&) { return "eps1, eps2"; }
 const char* eps_names(const dcor_hrs_segment&) { return "eps"; }
 const char* eps_names(const dcor_hrs_pair_segment&) { return "eps"; }
+bool eps_ok(const dcor_subg_pair_segment& g) {
+  return g.eps1 > 0.0 && g.eps2 > 0.0 && std::isfinite(g.eps1) && std::isfinite(g.eps2);
+}
 const char* eps_names(const dcor_subg_segment&) { return "finite eps1, eps2"; }
+const char* eps_names(const dcor_subg_pair_segment&) { return "finite eps1, eps2"; }
 template <class Seg> int check_columns(const char*, const Seg&, int64_t, int64_t) { return DCOR_OK; }
 template <class Seg> int columns_in_range(const char* entry, const Seg& g, int64_t i, int64_t p) {
   if (g.col_x < 0 || g.col_x >= p || g.col_y < 0 || g.col_y >= p)
@@ -239,6 +243,9 @@ int check_columns(const char* entry, const dcor_sign_pair_segment& g, int64_t i,
   return columns_in_range(entry, g, i, p);
 }
 int check_columns(const char* entry, const dcor_hrs_pair_segment& g, int64_t i, int64_t p) {
+  return columns_in_range(entry, g, i, p);
+}
+int check_columns(const char* entry, const dcor_subg_pair_segment& g, int64_t i, int64_t p) {
   return columns_in_range(entry, g, i, p);
 }
 void set_columns(SignSegConst&, const dcor_sign_segment&) {}
@@ -312,6 +319,33 @@ void hrs_segment_record(const PrematSubgConst& pc, const Seg& g, int64_t first, 
   t.ni0 = (uint32_t)g.seed_ni; t.ni1 = (uint32_t)(g.seed_ni >> 32);
   t.in0 = (uint32_t)g.seed_int; t.in1 = (uint32_t)(g.seed_int >> 32);
   t.rep_begin = (uint32_t)g.rep_begin;
+  t.first = first; t.out_row = g.out_row;
+}
+
+// The device-table record of a sub-G panel segment from its launch constants a (make_subg's values,
+// unchanged), its key and its place in the call; its batch size m joins `slots` when it is new (the
+// slots are the distinct m in order of first use, off the sum of the k before).
+template <class Seg>
+void subg_segment_record(const SubgConst& a, const Seg& g, int64_t first, std::vector<SubgMeanSlot>& slots,
+                         SubgSegConst& t) {
+  size_t d = 0;
+  while (d < slots.size() && slots[d].m != a.m) ++d;
+  if (d == slots.size()) {   // a batch size not seen before: its k means follow the others'
+    SubgMeanSlot sl;
+    std::memset(&sl, 0, sizeof(sl));
+    sl.k = a.k; sl.off = slots.empty() ? 0 : slots.back().off + slots.back().k;
+    sl.m = a.m; sl.md_pow2 = a.md_pow2; sl.md = a.md; sl.inv_md = a.inv_md;
+    slots.push_back(sl);
+  }
+  std::memset(&t, 0, sizeof(t));
+  t.k = a.k; t.m = a.m; t.md_pow2 = a.md_pow2; t.sender_is_X = a.sender_is_X;
+  t.m_slot = (int32_t)d;
+  t.md = a.md; t.kd = a.kd; t.inv_md = a.inv_md;
+  t.bx = a.bx; t.by = a.by; t.m_over_k = a.m_over_k; t.sqrt_k = a.sqrt_k;
+  t.ls = a.ls; t.lr = a.lr; t.bs = a.bs; t.s_central = a.s_central; t.sn2x2 = a.sn2x2; t.eps_r = a.eps_r;
+  t.k0 = (uint32_t)g.seed; t.k1 = (uint32_t)(g.seed >> 32);
+  t.rep_begin = (uint32_t)g.rep_begin;
+  t.mean_off = slots[d].off;
   t.first = first; t.out_row = g.out_row;
 }
 
@@ -492,7 +526,7 @@ int plan_subg_panel(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs
   }
   if (int st = segment_heads("subg_panel", segs, nseg, 0, items)) return st;
   // every segment's launch constants: make_subg's own, the simulation variant (hrs = 0, no override)
-  int64_t first = 0, nmeans = 0;
+  int64_t first = 0;
   for (int64_t i = 0; i < nseg; ++i) {
     const dcor_subg_segment& g = segs[i];
     SubgConst a;
@@ -501,28 +535,66 @@ int plan_subg_panel(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs
       return st;
     if (g.reps == 0) continue;
     if (tab.empty()) *c0 = a;
-    size_t d = 0;
-    while (d < slots.size() && slots[d].m != a.m) ++d;
-    if (d == slots.size()) {   // a batch size not seen before: its k means follow the others'
-      SubgMeanSlot sl;
-      std::memset(&sl, 0, sizeof(sl));
-      sl.k = a.k; sl.off = nmeans; sl.m = a.m; sl.md_pow2 = a.md_pow2; sl.md = a.md; sl.inv_md = a.inv_md;
-      nmeans += a.k;
-      slots.push_back(sl);
-    }
     SubgSegConst t;
-    std::memset(&t, 0, sizeof(t));
-    t.k = a.k; t.m = a.m; t.md_pow2 = a.md_pow2; t.sender_is_X = a.sender_is_X;
-    t.m_slot = (int32_t)d;
-    t.md = a.md; t.kd = a.kd; t.inv_md = a.inv_md;
-    t.bx = a.bx; t.by = a.by; t.m_over_k = a.m_over_k; t.sqrt_k = a.sqrt_k;
-    t.ls = a.ls; t.lr = a.lr; t.bs = a.bs; t.s_central = a.s_central; t.sn2x2 = a.sn2x2; t.eps_r = a.eps_r;
-    t.k0 = (uint32_t)g.seed; t.k1 = (uint32_t)(g.seed >> 32);
-    t.rep_begin = (uint32_t)g.rep_begin;
-    t.mean_off = slots[d].off;
-    t.first = first; t.out_row = g.out_row;
+    subg_segment_record(a, g, first, slots, t);
     first += g.reps;
     tab.push_back(t);
+  }
+  return DCOR_OK;
+}
+
+int plan_subg_table(const dcor_subg_table_desc* t, const dcor_subg_pair_segment* segs, int64_t nseg,
+                    std::vector<SubgPairSegConst>& tab, std::vector<SubgMeanSlot>& slots,
+                    std::vector<double>& clips, SubgConst* c0, int64_t* items) {
+  *items = 0;
+  if (!t->D || !t->eta) return fail(DCOR_EINVAL, "subg_table: null argument (D, eta)");
+  if ((uintptr_t)t->D & 7) return fail(DCOR_EINVAL, "subg_table: D must be aligned to 8 bytes");
+  if (t->n < 1 || t->n > 0x7fffffffLL)
+    return fail(DCOR_EINVAL, "subg_table: n must be in [1, 2^31) (got %lld)", (long long)t->n);
+  if (t->p < 1 || t->p > 0x7fffffffLL)
+    return fail(DCOR_EINVAL, "subg_table: p must be in [1, 2^31) (got %lld)", (long long)t->p);
+  if (t->ld < t->n)
+    return fail(DCOR_EINVAL, "subg_table: ld = %lld < n = %lld", (long long)t->ld, (long long)t->n);
+  if (!SubgTableLayout(0, 0, 0, t->n, t->p).ok)
+    return fail(DCOR_EINVAL, "subg_table: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)",
+                (long long)t->p, (long long)t->n);
+  for (int64_t c = 0; c < t->p; ++c)
+    if (!std::isfinite(t->eta[c]) || !(t->eta[c] > 0.0))
+      return fail(DCOR_EINVAL, "subg_table: column %lld: eta must be finite and > 0 (got %g)", (long long)c,
+                  t->eta[c]);
+  {  // alpha and nsim, as every segment's make_subg would refuse them
+    MixConst mx;
+    if (int st = check_common(t->n, 1.0, 1.0, t->alpha)) return st;
+    if (int st = make_mix(t->nsim, t->alpha, mx)) return st;
+  }
+  if (int st = segment_heads("subg_table", segs, nseg, t->p, items)) return st;
+  // every segment's launch constants: those of the reference call on its pair, eta and eps
+  int64_t first = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_subg_pair_segment& g = segs[i];
+    SubgConst a;
+    if (int st = make_subg(t->n, g.eps1, g.eps2, t->eta[g.col_x], t->eta[g.col_y], t->alpha, 0, NAN, NAN, NAN,
+                           NAN, NAN, NAN, t->nsim, a, nullptr, nullptr))
+      return st;
+    if (g.reps == 0) continue;
+    if (tab.empty()) {   // the call-wide constants alone: nothing of eta, eps or the key
+      std::memset(c0, 0, sizeof(*c0));
+      c0->n = a.n; c0->nd = a.nd; c0->sqrt_n = a.sqrt_n; c0->crit = a.crit; c0->mix = a.mix;
+    }
+    SubgPairSegConst r;
+    std::memset(&r, 0, sizeof(r));
+    subg_segment_record(a, g, first, slots, r);
+    r.col_x = g.col_x; r.col_y = g.col_y;
+    first += g.reps;
+    tab.push_back(r);
+  }
+  const int64_t nmeans = slots.empty() ? 0 : slots.back().off + slots.back().k;
+  if (!SubgTableLayout((int64_t)tab.size(), (int64_t)slots.size(), nmeans, t->n, t->p).ok)
+    return fail(DCOR_EINVAL, "subg_table: scratch bytes overflow (p = %lld, n = %lld, %lld batch means per column)",
+                (long long)t->p, (long long)t->n, (long long)nmeans);
+  if (!tab.empty()) {   // make_subg's own expression for l1 / l2, so the reference call's clips are these bits
+    clips.resize((size_t)t->p);
+    for (int64_t c = 0; c < t->p; ++c) clips[(size_t)c] = dcor_lambda_n((double)t->n, t->eta[c]);
   }
   return DCOR_OK;
 }

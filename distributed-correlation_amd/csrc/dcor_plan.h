@@ -1,5 +1,5 @@
 // dcor_plan.h -- the host decisions that need no device: the error reporter, the argument checks,
-// every launch constant (R operation order, cited) and the segment planners of the six
+// every launch constant (R operation order, cited) and the segment planners of the seven
 // segment-list entries.  Plain C++: neither this header nor dcor_plan.cpp includes the HIP
 // runtime, so the unit compiles, runs and is sanitized with a host compiler alone
 // (tests/host/plan_check.cpp).  Not part of the ABI.
@@ -130,6 +130,19 @@ int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* se
 int plan_subg_panel(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs, int64_t nseg,
                     std::vector<SubgSegConst>& tab, std::vector<SubgMeanSlot>& slots, SubgConst* c0,
                     int64_t* items);
+
+// dcor_subg_table_launch.  The reference call of a segment (include/dcor.h): dcor_subg_panel_launch
+// on X = column col_x, Y = column col_y with eta1 = eta[col_x], eta2 = eta[col_y].  Every check of
+// the entry after its null checks of t, segs and d_out, in the header's order (D and eta, D's
+// alignment, n, p, ld, the columns' scratch, every eta[c], alpha, nsim, then the segments' fields,
+// columns and ranges, the replicate cap, every segment's constants, the whole scratch), then the
+// table: a kept segment's record holds, field for field, what plan_subg_panel builds for the
+// reference call, and its columns.  slots: as plan_subg_panel's; clips: the p NI clips
+// lambda_n(n, eta[c]) (make_subg's expression for l1 / l2; empty when nothing is kept); c0: n, nd,
+// sqrt_n, crit and mix, everything else zero; items: the call's replicates.
+int plan_subg_table(const dcor_subg_table_desc* t, const dcor_subg_pair_segment* segs, int64_t nseg,
+                    std::vector<SubgPairSegConst>& tab, std::vector<SubgMeanSlot>& slots,
+                    std::vector<double>& clips, SubgConst* c0, int64_t* items);
 
 #pragma GCC visibility pop
 

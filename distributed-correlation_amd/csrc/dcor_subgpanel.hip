@@ -20,6 +20,14 @@
 // 32-byte read) at a time, one DCOR_SITE_DGP_B block and one table-driven log per sample.  NI: the
 // threads stride over the k prepared batch means, one DCOR_SITE_NI_LAP block per batch.  The log
 // table is read from LDS: a gather from global memory would wait behind the panel loads.
+//
+// The table form (dcor_subg_table_launch): k_subg_table_prep copies every column of a shared table
+// to a 32-B aligned pitch and writes, for every column and every distinct m, the k batch means of
+// the column clipped at its own lambda_n -- once per (column, m), not once per pair -- with
+// k_subg_panel_prep's arithmetic (sgp_batch_means is the one loop); k_subg_table is k_subg_panel's
+// shell with the segment's two columns and two mean rows taken from the segment table.  A
+// replicate is subg_panel_item in both, templated on where a sample pair and a batch's two means
+// come from, so its operation order is one piece of code.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -31,6 +39,25 @@ namespace dcor {
 
 #define SGP_PREP_NT 256
 #define SGP_PREP_MAXGRID 1024
+
+// Batch j's means of NC columns, column c clipped at l[c]: the clipped samples added in index
+// order, then sum * inv_md for m a power of two and sum / md otherwise (subg_fused_core's
+// arithmetic).  A column's mean depends on that column alone.
+template <int NC>
+__device__ __forceinline__ void sgp_batch_means(const double* const (&col)[NC], const double (&l)[NC], int64_t j,
+                                                int32_t m, int32_t pow2, double md, double inv_md,
+                                                double (&mean)[NC]) {
+  double s[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) s[c] = 0.0;
+  const int64_t i0 = j * m;   // samples j m .. j m + m - 1 < k m <= n
+  for (int32_t r = 0; r < m; ++r) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) s[c] += rclip(col[c][i0 + r], l[c]);    // ver-cor-subG.R:33-34
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) mean[c] = pow2 ? s[c] * inv_md : s[c] / md;
+}
 
 __global__ __launch_bounds__(SGP_PREP_NT) void k_subg_panel_prep(const double* __restrict__ X,
                                                                  const double* __restrict__ Y, int64_t n,
@@ -47,14 +74,46 @@ __global__ __launch_bounds__(SGP_PREP_NT) void k_subg_panel_prep(const double* _
     const int64_t k = slots[d].k, off = slots[d].off;
     const int32_t m = slots[d].m, pow2 = slots[d].md_pow2;
     const double md = slots[d].md, inv_md = slots[d].inv_md;
-    for (int64_t j = gt; j < k; j += gs) {   // batch j: samples j m .. j m + m - 1 < k m <= n
-      double sx = 0.0, sy = 0.0;
-      const int64_t i0 = j * m;
-      for (int32_t r = 0; r < m; ++r) {
-        sx += rclip(X[i0 + r], l1);                                      // ver-cor-subG.R:33
-        sy += rclip(Y[i0 + r], l2);                                      // :34
-      }
-      means[off + j] = make_double2(pow2 ? sx * inv_md : sx / md, pow2 ? sy * inv_md : sy / md);
+    const double* const col[2] = {X, Y};
+    const double l[2] = {l1, l2};
+    for (int64_t j = gt; j < k; j += gs) {
+      double mean[2];
+      sgp_batch_means<2>(col, l, j, m, pow2, md, inv_md, mean);
+      means[off + j] = make_double2(mean[0], mean[1]);
+    }
+  }
+}
+
+// The table's preparation, in tiles of SGP_PREP_NT consecutive values of one column taken at a
+// stride of the grid (p is not a grid dimension).  The copy: column c of D (at D + c ld) to
+// cols + c npad, zeros from n on.  The means: for every slot d, batch j of column c clipped at
+// clips[c] to means[c mpitch + off_d + j] -- one thread owns a batch, the bits k_subg_panel_prep
+// writes for that column on either side.  Every value has one writer; nothing depends on the grid.
+__global__ __launch_bounds__(SGP_PREP_NT) void k_subg_table_prep(const double* __restrict__ D, int64_t ld,
+                                                                 int64_t n, int64_t npad, int64_t p,
+                                                                 const double* __restrict__ clips,
+                                                                 const SubgMeanSlot* __restrict__ slots_g,
+                                                                 int nslots, double* __restrict__ cols,
+                                                                 double* __restrict__ means, int64_t mpitch) {
+  const int64_t ct = (npad + SGP_PREP_NT - 1) / SGP_PREP_NT;
+  for (int64_t t = blockIdx.x; t < p * ct; t += gridDim.x) {
+    const int64_t c = t / ct, i = (t - c * ct) * SGP_PREP_NT + threadIdx.x;
+    if (i < npad) cols[c * npad + i] = i < n ? D[c * ld + i] : 0.0;
+  }
+  const SegTab<SubgMeanSlot> slots = (SegTab<SubgMeanSlot>)slots_g;
+  for (int d = 0; d < nslots; ++d) {
+    const int64_t k = slots[d].k, off = slots[d].off;
+    const int32_t m = slots[d].m, pow2 = slots[d].md_pow2;
+    const double md = slots[d].md, inv_md = slots[d].inv_md;
+    const int64_t kt = (k + SGP_PREP_NT - 1) / SGP_PREP_NT;
+    for (int64_t t = blockIdx.x; t < p * kt; t += gridDim.x) {
+      const int64_t c = t / kt, j = (t - c * kt) * SGP_PREP_NT + threadIdx.x;
+      if (j >= k) continue;
+      const double* const col[1] = {D + c * ld};
+      const double l[1] = {clips[c]};
+      double mean[1];
+      sgp_batch_means<1>(col, l, j, m, pow2, md, inv_md, mean);
+      means[c * mpitch + off + j] = mean[0];
     }
   }
 }
@@ -70,8 +129,33 @@ struct SubgPackedLoad {
   }
 };
 
+// The batch means of the packed panel's entry: (X-bar_j, Y-bar_j) in one 16-byte read.
+struct SubgPackedMeans {
+  const double2* __restrict__ bm;
+  __device__ __forceinline__ double2 at(uint32_t j) const { return bm[j]; }
+};
+
+// The table's loader: samples 2 q and 2 q + 1 as one 16-byte read from each of the pair's two
+// columns (coalesced, 1 KB per wave-instruction and column; a column is padded with zeros to a
+// multiple of 4 samples and starts 32-B aligned), and its means: batch j of the two columns' rows.
+struct SubgColumnLoad {
+  const double2* __restrict__ xa;
+  const double2* __restrict__ yb;
+  __device__ __forceinline__ void pair(uint32_t q, double2& a, double2& b) const {
+    const double2 x = xa[q], y = yb[q];
+    a = make_double2(x.x, y.x);
+    b = make_double2(x.y, y.y);
+  }
+};
+struct SubgColumnMeans {
+  const double* __restrict__ mx;
+  const double* __restrict__ my;
+  __device__ __forceinline__ double2 at(uint32_t j) const { return make_double2(mx[j], my[j]); }
+};
+
 // The segment's fields over the call-wide ones in c (scalar loads: the address is uniform).
-__device__ __forceinline__ void sgp_seg_load(SegTab<SubgSegConst> tab, int s, SubgConst& c) {
+template <class Seg>
+__device__ __forceinline__ void sgp_seg_load(SegTab<Seg> tab, int s, SubgConst& c) {
   c.k = tab[s].k; c.m = tab[s].m; c.md_pow2 = tab[s].md_pow2; c.sender_is_X = tab[s].sender_is_X;
   c.md = tab[s].md; c.kd = tab[s].kd; c.inv_md = tab[s].inv_md;
   c.bx = tab[s].bx; c.by = tab[s].by; c.m_over_k = tab[s].m_over_k; c.sqrt_k = tab[s].sqrt_k;
@@ -93,12 +177,13 @@ template <int VPL> struct SgpLds<false, VPL> {
 };
 
 // Replicate `rep` of the segment with constants c.  load.pair(q, a, b) gives samples 2 q, 2 q + 1
-// as (x, y) (zeros past n); bm: the k batch means of the segment's m; lt: the log table in LDS.
+// as (x, y) (zeros past n); bm.at(j): batch j's two means at the segment's m; lt: the log table in
+// LDS.
 // A NaN sample is seen by the unordered compare, not by the clips (v_min / v_max drop it), and
 // reaches the INT sums once, before the reduction; the NI side's NaN is in the prepared means.
-template <bool WAVE, int VPL, class Load>
-__device__ __forceinline__ void subg_panel_item(const SubgConst& c, uint32_t rep, Load load,
-                                                const double2* __restrict__ bm, const double2* lt,
+template <bool WAVE, int VPL, class Load, class Means>
+__device__ __forceinline__ void subg_panel_item(const SubgConst& c, uint32_t rep, Load load, Means bm,
+                                                const double2* lt,
                                                 SgpLds<WAVE, VPL>& lds, dcor_rep_out* dst) {
   constexpr uint32_t NT = WAVE ? 64 : DCOR_BLOCK;
   const uint32_t tid = WAVE ? (threadIdx.x & 63u) : threadIdx.x;
@@ -127,7 +212,7 @@ __device__ __forceinline__ void subg_panel_item(const SubgConst& c, uint32_t rep
   if (c.sender_is_X) int_stream(std::true_type{}); else int_stream(std::false_type{});
   // NI: batch j's prepared means meet its Laplace pair (:48-55)
   for (uint32_t j = tid; j < k; j += NT) {
-    const double2 mb = bm[j];
+    const double2 mb = bm.at(j);
     const U4 w = draw(j, rep, DCOR_SITE_NI_LAP, c.k0, c.k1);
     const double xt = mb.x + c.bx * unit_laplace_t(u53(w.w0, w.w1), lt);   // :48
     const double yt = mb.y + c.by * unit_laplace_t(u53(w.w2, w.w3), lt);   // :49
@@ -183,6 +268,45 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_subg_panel(SubgConst c,
     // the previous item's readers of the epilogue's LDS are done
     if constexpr (WAVE) wave_sync(); else __syncthreads();
     const uint32_t rep = (uint32_t)c.rep_begin + (uint32_t)(it - cur.first);
+    subg_panel_item<WAVE, VPL>(c, rep, load, SubgPackedMeans{bm}, lds.lt, lds, out + out_row + (it - cur.first));
+  }
+}
+
+// The same shell over a table's column pairs: the segment's columns (pitch doubles apart in cols)
+// and their rows of batch means (mpitch doubles apart in means) change with the segment, read at
+// wave-uniform addresses.  c holds n, nd, sqrt_n, crit and mix; everything else is the segment's.
+// The waves per SIMD asked for are the panel kernels' (LDS-bound 2 and 3 in the wave forms): the
+// four pointers of a pair must not cost the workgroup form its fourth wave.
+template <bool WAVE, int VPL>
+__global__ __launch_bounds__(DCOR_BLOCK, WAVE ? (VPL == 32 ? 2 : 3) : 4) void k_subg_table(SubgConst c,
+                                                           const SubgPairSegConst* __restrict__ tab_g, int nseg,
+                                                           int64_t items, const double* __restrict__ cols,
+                                                           int64_t pitch, const double* __restrict__ means,
+                                                           int64_t mpitch, dcor_rep_out* __restrict__ out) {
+  __shared__ SgpLds<WAVE, VPL> lds;
+  const SegTab<SubgPairSegConst> tab = (SegTab<SubgPairSegConst>)tab_g;
+  log_tab_to_lds(lds.lt, DCOR_BLOCK);
+  __syncthreads();
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t unit = WAVE ? (int64_t)blockIdx.x * DCOR_WAVES + wv : (int64_t)blockIdx.x;
+  const int64_t units = WAVE ? (int64_t)gridDim.x * DCOR_WAVES : (int64_t)gridDim.x;
+  SubgColumnLoad load{nullptr, nullptr};
+  SubgColumnMeans bm{nullptr, nullptr};
+  SegCursor cur;
+  int64_t out_row = 0;
+  for (int64_t it = unit; it < items; it += units) {
+    cur.seek(tab, nseg, items, it, [&](int s) {
+      sgp_seg_load(tab, s, c);
+      const int64_t a = tab[s].col_x, b = tab[s].col_y, off = tab[s].mean_off;
+      load.xa = (const double2*)(cols + a * pitch);
+      load.yb = (const double2*)(cols + b * pitch);
+      bm.mx = means + a * mpitch + off;
+      bm.my = means + b * mpitch + off;
+      out_row = tab[s].out_row;
+    });
+    // the previous item's readers of the epilogue's LDS are done
+    if constexpr (WAVE) wave_sync(); else __syncthreads();
+    const uint32_t rep = (uint32_t)c.rep_begin + (uint32_t)(it - cur.first);
     subg_panel_item<WAVE, VPL>(c, rep, load, bm, lds.lt, lds, out + out_row + (it - cur.first));
   }
 }
@@ -213,6 +337,35 @@ int launch_subg_panel(const SubgConst& c, const double* X, const double* Y, cons
   else
     hipLaunchKernelGGL((k_subg_panel<true, 16>), g, b, 0, st, c, tab, nseg, items, (const double2*)xy,
                        (const double2*)means, out);
+  return (int)hipGetLastError();
+}
+
+int launch_subg_table(const SubgConst& c, const double* D, int64_t p, int64_t ld, const double* clips,
+                      const SubgMeanSlot* slots, int nslots, double* means, int64_t mpitch, double* cols,
+                      int64_t npad, const SubgPairSegConst* tab, int nseg, int64_t items, dcor_rep_out* out,
+                      void* stream) {
+  if (items <= 0 || nseg <= 0 || nslots <= 0 || p <= 0) return 0;
+  const bool wave = c.n <= SUBG_W_NMAX;   // a function of n alone (as launch_subg_panel)
+  const void* kern = wave ? (c.mix.nsim > 1024 ? (const void*)k_subg_table<true, 32>
+                                               : (const void*)k_subg_table<true, 16>)
+                          : (const void*)k_subg_table<false, 16>;
+  int64_t grid = 0;
+  const int64_t units = wave ? (items + DCOR_WAVES - 1) / DCOR_WAVES : items;
+  if (int e = persistent_grid(kern, DCOR_BLOCK, 0, units, &grid)) return e;
+  // the copy has the most tiles of the preparation's phases (k <= n)
+  int64_t pg = p * ((npad + SGP_PREP_NT - 1) / SGP_PREP_NT);
+  if (pg > SGP_PREP_MAXGRID) pg = SGP_PREP_MAXGRID;
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_subg_table_prep, dim3((unsigned)pg), dim3(SGP_PREP_NT), 0, st, D, ld, c.n, npad, p, clips,
+                     slots, nslots, cols, means, mpitch);
+  const dim3 g((unsigned)grid), b(DCOR_BLOCK);
+  const double *cc = cols, *cm = means;
+  if (!wave)
+    hipLaunchKernelGGL((k_subg_table<false, 16>), g, b, 0, st, c, tab, nseg, items, cc, npad, cm, mpitch, out);
+  else if (c.mix.nsim > 1024)
+    hipLaunchKernelGGL((k_subg_table<true, 32>), g, b, 0, st, c, tab, nseg, items, cc, npad, cm, mpitch, out);
+  else
+    hipLaunchKernelGGL((k_subg_table<true, 16>), g, b, 0, st, c, tab, nseg, items, cc, npad, cm, mpitch, out);
   return (int)hipGetLastError();
 }
 

@@ -147,6 +147,18 @@ class HrsPairSegment(C.Structure):
     _fields_ = HrsSegment._fields_ + [("col_x", C.c_int32), ("col_y", C.c_int32)]
 
 
+class SubgTableDesc(C.Structure):
+    """dcor_subg_table_desc (include/dcor.h): the shared table (p columns of n samples, ld apart), its
+    per-column sub-Gaussian parameters (a HOST array of p doubles) and the call-wide settings."""
+    _fields_ = [("n", C.c_int64), ("p", C.c_int64), ("ld", C.c_int64), ("D", _P), ("eta", _D),
+                ("alpha", C.c_double), ("nsim", C.c_int64)]
+
+
+class SubgPairSegment(C.Structure):
+    """dcor_subg_pair_segment (include/dcor.h): a dcor_subg_segment and its (X, Y) columns."""
+    _fields_ = SubgSegment._fields_ + [("col_x", C.c_int32), ("col_y", C.c_int32)]
+
+
 class RsDraws(C.Structure):
     """dcor_rs_draws: host buffers of the R-stream mode's materialised draws."""
     _fields_ = [("X", _D), ("Y", _D), ("lap_ni_sc", _D), ("lap_int_sc", _D), ("lap_ni_x", _D),
@@ -210,6 +222,8 @@ SIGNATURES = {
     "dcor_hrs_table_launch": (C.c_int, [C.POINTER(HrsTableDesc), C.POINTER(HrsPairSegment), C.c_int64,
                                         _P, _P]),
     "dcor_subg_panel_launch": (C.c_int, [C.POINTER(SubgPanelDesc), C.POINTER(SubgSegment), C.c_int64,
+                                         _P, _P]),
+    "dcor_subg_table_launch": (C.c_int, [C.POINTER(SubgTableDesc), C.POINTER(SubgPairSegment), C.c_int64,
                                          _P, _P]),
     "dcor_batch_geometry": (C.c_int, [C.c_int64, C.c_double, C.c_double, C.c_int, C.c_int, _I64]),
     "dcor_ci_ni_signbatch": (C.c_int, [_D, _D, C.c_int64, C.c_double, C.c_double, C.c_double,

@@ -273,6 +273,18 @@ def subg_panel_distributed(X, Y, segs, group=None, **kw):
     return _segments_distributed(lambda mine: subgpanel.sweep_segments(X, Y, mine, **kw), segs, 3, 4, group)
 
 
+def subg_table_distributed(D, segs, group=None, **kw):
+    """dcor.subgpanel.table_segments over G ranks, as sign_table_distributed: the flattened (segment,
+    replicate) space of segs [(col_x, col_y, eps1, eps2, seed, rep_begin, reps), ...] is split into
+    contiguous per-rank ranges (segment_shard), each rank runs its pieces -- the segment's pair, eps
+    pair and key, rep_begin moved on by the piece's offset -- in one native call, and the records are
+    all-gathered in rank order.  A record depends only on (columns, their eta, eps1, eps2, seed,
+    replicate), so the [sum(reps), 6] result, identical on all ranks, equals one process's
+    table_segments(D, segs) byte for byte."""
+    from . import subgpanel
+    return _segments_distributed(lambda mine: subgpanel.table_segments(D, mine, **kw), segs, 5, 6, group)
+
+
 def hrs_table_distributed(Z, lam, segs, group=None, **kw):
     """dcor.hrs.table_segments over G ranks, as sign_table_distributed: the flattened (segment,
     replicate) space of segs [(col_x, col_y, eps, seed_ni, seed_int, rep_begin, reps), ...] is split

@@ -565,6 +565,55 @@ typedef struct dcor_subg_segment {
 int dcor_subg_panel_launch(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream);
 
+/* The same sub-G replicates for any column pairs of one shared table (vertically partitioned data:
+ * several variables on either server, the private correlation of every pair): the table form of
+ * dcor_subg_panel_launch, as dcor_sign_table_launch is of dcor_sign_panel_launch.  D holds p
+ * columns of n samples, column c at D + c * ld, and eta[c] is column c's sub-Gaussian parameter.
+ * A segment names its pair: X = column col_x, Y = column col_y; (a, b) and (b, a) are different
+ * segments and col_x == col_y is allowed.  The records of a segment equal, byte for byte, the
+ * records of dcor_subg_panel_launch on X = column col_x, Y = column col_y with eta1 = eta[col_x],
+ * eta2 = eta[col_y] and the same alpha, nsim, eps1, eps2, seed, rep_begin and reps (the segment's
+ * reference call): the same per-replicate code, the same draw sites (DCOR_SITE_SCALAR block 4,
+ * DCOR_SITE_NI_LAP, DCOR_SITE_DGP_B words 2,3, DCOR_SITE_MIX_Z, DCOR_SITE_MIX_L), the same geometry
+ * (m = ceil(8 / (eps1 eps2)) capped at n, k = floor(n / m)), the same sender rule (X sends iff
+ * eps1 >= eps2) and the same wave / workgroup choice, a function of n alone.  A NaN in a column
+ * reaches only the pairs that name it, under the panel entry's rule: within the first k m samples it
+ * makes the NI columns NaN, anywhere in the column the INT columns.  A record depends only on
+ * (columns, their eta, eps1, eps2, seed, replicate), never on the segment split, the order of
+ * segments, out_row or the launch.  One preparation launch (every column copied to a padded pitch,
+ * and for every column and every distinct batch size m of the call the k batch means of the column
+ * clipped at its own lambda_n(n, eta[c]): a column is clipped and summed once per distinct m, not
+ * once per pair, in the panel entry's arithmetic, every value with one writer) and one replicate
+ * launch cover every pair and every (eps1, eps2); nothing that depends on eta is call-wide, a
+ * segment's constants come from a device table.
+ * Checks, all before anything is enqueued and before any device access (an invalid call returns
+ * its code and leaves d_out untouched; dcor_last_error names the segment or the column): non-null
+ * t, D, eta, segs, d_out; D aligned to 8 bytes; 1 <= n < 2^31; 1 <= p < 2^31; ld >= n; p * npad * 8
+ * scratch bytes representable (npad: n rounded up to a multiple of 4; before eta is read); every
+ * eta[c] finite and > 0; alpha, nsim (<= 2048) as dcor_sim_launch; per segment eps1, eps2 > 0 and
+ * finite, reps, rep_begin, out_row >= 0, rep_begin + reps <= 2^32, 0 <= col_x, col_y < p; at most
+ * 2^31 - 1 replicates per call; the whole scratch's bytes representable.  nseg == 0 or no replicates at all
+ * returns DCOR_OK with no device work.  Asynchronous on `stream`, no host synchronisation; scratch
+ * is stream-ordered (8 B per sample and column, 8 B per column, batch and distinct m, 8 B per
+ * column, the segment and slot tables) -- no noise array; a warm second call of the same shape
+ * makes no device allocation.  D, eta and segs are borrowed for the call only (D until the call's
+ * work on `stream` has run). */
+typedef struct dcor_subg_table_desc {
+  int64_t n, p, ld;        /* samples per column, columns, elements between column starts */
+  const double* D;         /* DEVICE, column c = D + c * ld; borrowed for the call */
+  const double* eta;       /* HOST, [p]: column c's sub-Gaussian parameter, finite and > 0 */
+  double alpha;
+  int64_t nsim;
+} dcor_subg_table_desc;
+typedef struct dcor_subg_pair_segment {
+  double eps1, eps2;
+  uint64_t seed;
+  int64_t rep_begin, reps, out_row;
+  int32_t col_x, col_y;    /* X = column col_x, Y = column col_y */
+} dcor_subg_pair_segment;
+int dcor_subg_table_launch(const dcor_subg_table_desc* t, const dcor_subg_pair_segment* segs,
+                           int64_t nseg, dcor_rep_out* d_out, void* stream);
+
 int dcor_premat_sign_launch(const dcor_premat_sign* d, dcor_rep_out* d_out, void* stream);
 int dcor_premat_subg_launch(const dcor_premat_subg* d, dcor_rep_out* d_out, void* stream);
 
