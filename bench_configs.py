@@ -668,6 +668,59 @@ def hrs_table(R, p=8, arm="both"):
         print(json.dumps({"config": "HT-check", "records_bit_equal": same}), flush=True)
 
 
+def hrs_table_na(R, p=4, gap=0.2, repeats=5):
+    """HTN: the HRS estimators on the pairwise-complete cases of a p-column stand-in table (n =
+    19,433, C5's row count) with about `gap` of every column's rows missing independently: the p (p -
+    1) / 2 pairs x 23 eps x R sweep in one dcor_hrs_table_pairwise_launch call (HTN), every pair on its
+    own n_ab rows.  Beside it the route before the entry, dcor_hrs_table_launch on the listwise-deleted
+    table (HTN-listwise: every pair on the rows no column misses), and the two entries on the
+    complete table (HTN-full, HTN-full-table: the same n per replicate, records bit-equal), which
+    compares k_hrs_pair_table's packed 16-B gathers with k_hrs_table's two 8-B ones directly.  Each
+    line: the median and the least of `repeats` timed calls after one warm-up.  Not in the default
+    list: reach it with --only HTN."""
+    import numpy as np
+    import torch
+    from dcor import hrs, signpanel
+    n = 19433
+    Z = signpanel.standin_table(n, p, 0.3)
+    lam = np.array([2.0 + 0.1 * c for c in range(p)])
+    pairs = signpanel.all_pairs(p)
+    ne = len(hrs.EPS_GRID)
+    V = np.random.default_rng(11).random((n, p)) >= gap
+    Zna = np.asfortranarray(np.where(V, Z, np.nan))
+    Zlist = np.asfortranarray(Z[V.all(axis=1)])
+    valid, full = hrs.valid_mask(Zna), hrs.valid_mask(Z)
+    segs = [(a, b, e, 10 + 1000 * (j * ne + idx), 20 + 1000 * (j * ne + idx), 0, R)
+            for j, (a, b) in enumerate(pairs) for idx, e in enumerate(hrs.EPS_GRID, start=1)]
+    n_pair = [int((V[:, a] & V[:, b]).sum()) for a, b in pairs]
+    total = len(segs) * R
+    pk = "k_hrs_pair_pack + k_hrs_pair_table + k_hrs_sweep_fused_epilogue"
+    tk = "k_hrs_table_prep + k_hrs_table + k_hrs_sweep_fused_epilogue"
+    res = {}
+    for name, fn, rows, kernel in (
+            ("HTN", lambda: hrs.pairwise_segments(Zna, lam, segs, valid=valid), n_pair, pk),
+            ("HTN-listwise", lambda: hrs.table_segments(Zlist, lam, segs), [len(Zlist)] * len(pairs), tk),
+            ("HTN-full", lambda: hrs.pairwise_segments(Z, lam, segs, valid=full), [n] * len(pairs), pk),
+            ("HTN-full-table", lambda: hrs.table_segments(Z, lam, segs), [n] * len(pairs), tk)):
+        fn()    # warm-up
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            res[name] = fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        t = float(np.median(ts))
+        samples = sum(rows) * ne * R     # samples every replicate of the call reads
+        line(name, n=n, p=p, pairs=len(pairs), rows_per_pair=rows, replicates=total, seconds=t,
+             seconds_min=min(ts), reps_per_s=total / t, sample_reps_per_s=samples / t,
+             finite=bool(np.isfinite(res[name]).all()), kernel=kernel,
+             note="host wall time of one call: table (and mask) upload, one preparation launch, one streaming "
+                  "and one epilogue launch over every (pair, eps) segment, records copied back")
+    same = bool(np.array_equal(res["HTN-full"].view(np.uint64), res["HTN-full-table"].view(np.uint64)))
+    print(json.dumps({"config": "HTN-check", "full_mask_records_bit_equal": same}), flush=True)
+
+
 def subg():
     from dcor.sim import CellSpec, simulate
     cell = CellSpec(n=100_000, rho=0.5, eps1=1.0, eps2=1.0, family="subG", dgp="bounded_factor", seed=5)
@@ -985,6 +1038,7 @@ def main():
     if "HT" in which: hrs_table(a.hs_R)
     if "HT-table" in which: hrs_table(a.hs_R, arm="table")
     if "HT-pairs" in which: hrs_table(a.hs_R, arm="pairs")
+    if "HTN" in which: hrs_table_na(a.hs_R)
     if "S" in which: subg()
     if "R1" in which: rstream_c1()
     if "RG" in which: rstream_grid()

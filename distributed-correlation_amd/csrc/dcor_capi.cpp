@@ -1151,6 +1151,30 @@ int dcor_hrs_table_launch(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segm
   }, false, {{lay.lam_off, t->lam, (size_t)t->p * sizeof(double)}});
 }
 
+int dcor_hrs_table_pairwise_launch(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair_segment* segs,
+                                   int64_t nseg, dcor_rep_out* d_out, void* stream) {
+  if (int st = seg_args("hrs_table_pairwise", t, segs, nseg, d_out)) return st;
+  if (nseg == 0) return DCOR_OK;   // nothing to run
+  std::vector<HrsPairNaSegConst> tab;
+  std::vector<HrsPairSlot> slots;
+  int64_t items = 0, max_km = 0, panel_elems = 0;
+  // p: the first kept segment's constants; the call-wide ones (crit, mix, hrs) are read from it,
+  // everything that depends on lam, eps or the pair's own count from the table
+  PrematSubgConst p;
+  if (int st = plan_hrs_table_pairwise(t, segs, nseg, tab, slots, &p, &panel_elems, &items, &max_km)) return st;
+  if (items == 0) return DCOR_OK;
+  if (int st = need_device()) return st;
+  p.X = p.Y = nullptr;
+  const HrsPairTableLayout lay(items, (int64_t)tab.size(), (int64_t)slots.size(), t->n, t->p, panel_elems);
+  return with_table("hrs_table_pairwise", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
+    return launch_hrs_pair_table(p, t->D, t->n, t->ld, lay.lam(buf), lay.masks(buf), lay.nw, lay.slots(buf),
+                                 (int)slots.size(), lay.panels(buf), lay.tab(buf), (int)tab.size(), items,
+                                 max_km, buf, d_out, stream);
+  }, false, {{lay.slot_off, slots.data(), slots.size() * sizeof(HrsPairSlot)},
+             {lay.lam_off, t->lam, (size_t)t->p * sizeof(double)},
+             {lay.mask_off, t->valid, (size_t)t->p * (size_t)lay.nw * sizeof(uint64_t)}});
+}
+
 int dcor_subg_panel_launch(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream) {
   if (int st = seg_args("subg_panel", p, segs, nseg, d_out)) return st;

@@ -392,6 +392,80 @@ int launch_hrs_table(const PrematSubgConst& c, const double* D, int64_t p, int64
                      double* cols, int64_t npad, const HrsPairSegConst* tab, int nseg, int64_t items,
                      int64_t max_km, void* part, dcor_rep_out* out, void* stream);
 
+// ---- the same on the pairwise-complete cases of a table with gaps (dcor_hrs_table_pairwise_launch) ----
+// A table segment whose sample count is its pair's own: n_ab = popcount(valid[col_x] & valid[col_y]).
+// What launch_hrs_table takes call-wide because it follows from n alone is per segment here: n, nd,
+// sqrt_n (make_subg's c.n, c.nd, c.sqrt_n: the permutation's range and the local-noise blocks of
+// hrs_fused_l2_item, the INT mean, sd, c* and width of premat_subg_pre / _post) and the Feistel split
+// pa, pc of ceil(log2 n) bits.  Every other n-dependent constant of make_subg (k, m and what follows
+// from them, lr through delta = 1 / n, s_central, sn2x2, crit_sqrt2_s) is in HrsSegConst already;
+// crit, mix and hrs do not depend on n and stay call-wide.  panel: the pair's packed panel, in
+// double2 elements from the first panel.
+// The Feistel split of ceil(log2 n) bits (launch_perm's): the HRS launchers' and the planner's.
+inline void hrs_feistel_split(int64_t n, int* pa, int* pc) {
+  int bits = 1;
+  while ((1ll << bits) < n) ++bits;
+  *pa = bits / 2; *pc = bits - *pa;
+}
+struct HrsPairNaSegConst : HrsPairSegConst {
+  int64_t n;
+  double nd, sqrt_n;
+  int32_t pa, pc;
+  int64_t panel;
+};
+static_assert(sizeof(HrsPairNaSegConst) == 208, "the pairwise table entry's device table stride");
+// A distinct ordered pair of a call ("slot"), in order of first use: its columns, its count of
+// pairwise-complete rows and its panel's first element (double2 elements from the first panel; each
+// panel starts 256-B aligned and holds n_ab rounded up to even elements, the pad one zero).
+struct HrsPairSlot {
+  int64_t n_ab, panel;
+  int32_t col_x, col_y;
+};
+static_assert(sizeof(HrsPairSlot) == 24, "the pairwise table entry's slot table stride");
+// double2 elements a slot's panel takes
+__host__ __device__ inline int64_t hrs_pair_panel_elems(int64_t n_ab) { return (n_ab + 15) & ~(int64_t)15; }
+// Pairwise HRS-table scratch: partials (one SubgPartial per replicate of the call) | the segment
+// table, then the slot table | the p clip bounds | the p masks of nw = ceil(n / 64) words | the
+// slots' packed panels (panel_elems double2 in all).  Every region starts 256-B aligned when the base
+// is.  ok is false when the total is not representable.
+struct HrsPairTableLayout {
+  int64_t nw;
+  size_t tab_off = 0, slot_off = 0, lam_off = 0, mask_off = 0, panel_off = 0, bytes = 0;
+  bool ok = false;
+  HrsPairTableLayout(int64_t items, int64_t nseg, int64_t nslot, int64_t n, int64_t p, int64_t panel_elems)
+      : nw((n + 63) >> 6) {
+    const size_t lim = SIZE_MAX / 2;
+    if (n < 1 || p < 1 || nseg < 0 || nslot < 0 || items < 0 || panel_elems < 0 || (size_t)p > lim / 16 ||
+        (size_t)nseg > lim / (2 * sizeof(HrsPairNaSegConst)) || (size_t)nslot > lim / (2 * sizeof(HrsPairSlot)) ||
+        (size_t)items > lim / (2 * sizeof(SubgPartial)) || (size_t)panel_elems > lim / (2 * sizeof(double2)))
+      return;
+    tab_off = al256((size_t)items * sizeof(SubgPartial));
+    slot_off = tab_off + al256((size_t)nseg * sizeof(HrsPairNaSegConst));
+    lam_off = slot_off + al256((size_t)nslot * sizeof(HrsPairSlot));
+    mask_off = lam_off + al256((size_t)p * sizeof(double));
+    const size_t col_bytes = (size_t)nw * sizeof(uint64_t);
+    if (mask_off > lim || (size_t)p > (lim - mask_off) / col_bytes) return;
+    panel_off = mask_off + al256((size_t)p * col_bytes);
+    if (panel_off > lim || (size_t)panel_elems * sizeof(double2) > lim - panel_off) return;
+    bytes = panel_off + (size_t)panel_elems * sizeof(double2);
+    ok = true;
+  }
+  HrsPairNaSegConst* tab(void* base) const { return (HrsPairNaSegConst*)((char*)base + tab_off); }
+  HrsPairSlot* slots(void* base) const { return (HrsPairSlot*)((char*)base + slot_off); }
+  double* lam(void* base) const { return (double*)((char*)base + lam_off); }
+  uint64_t* masks(void* base) const { return (uint64_t*)((char*)base + mask_off); }
+  double2* panels(void* base) const { return (double2*)((char*)base + panel_off); }
+};
+// The preparation launch (one workgroup per slot: the rows of valid[col_x] & valid[col_y] compacted
+// in order into the slot's panel, sample r = (rclip(D[col_x][i], lam[col_x]), rclip(D[col_y][i],
+// lam[col_y])), k_premat_xy_pack's bits) and the streaming and epilogue launches over `items`
+// replicates of the nseg >= 1 segments in `tab` (device), as launch_hrs_table.  c: any segment's
+// PrematSubgConst (crit, mix, hrs are call-wide); lam, masks (p x nw words), slots: device.
+int launch_hrs_pair_table(const PrematSubgConst& c, const double* D, int64_t n, int64_t ld, const double* lam,
+                          const uint64_t* masks, int64_t nw, const HrsPairSlot* slots, int nslot,
+                          double2* panels, const HrsPairNaSegConst* tab, int nseg, int64_t items,
+                          int64_t max_km, void* part, dcor_rep_out* out, void* stream);
+
 // ---- sub-G simulation estimators on a shared panel (dcor_subg_panel_launch; dcor_subgpanel.hip) ----
 // One segment of a sub-G panel call: the part of SubgConst that depends on the segment's (eps1,
 // eps2) (make_subg's values, unchanged; ls follows the sender's eta), its Philox key and its place

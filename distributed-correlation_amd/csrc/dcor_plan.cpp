@@ -1,6 +1,6 @@
 // dcor_plan.cpp -- the device-free half of the host side (dcor_plan.h): the error reporter, the
 // argument checks of the reference's stopifnot() calls, every data-independent scalar of the
-// estimators (R operation order, cited), and the segment planners of the seven segment-list
+// estimators (R operation order, cited), and the segment planners of the eight segment-list
 // entries.  No HIP: this file and the headers it includes compile with a host compiler alone.
 #include "dcor_plan.h"
 
@@ -9,6 +9,8 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <utility>
 
 namespace dcor {
 namespace host {
@@ -349,6 +351,30 @@ void subg_segment_record(const SubgConst& a, const Seg& g, int64_t first, std::v
   t.first = first; t.out_row = g.out_row;
 }
 
+// The checks the two HRS table entries share (T: dcor_hrs_table_desc or dcor_hrs_table_na_desc), in
+// the entries' order: p and ld; D's alignment and every lam[c]; alpha and nsim, as every segment's
+// make_subg would refuse them.
+template <class T> int hrs_table_shape(const char* entry, const T& t) {
+  if (t.p < 1 || t.p > 0x7fffffffLL)
+    return fail(DCOR_EINVAL, "%s: p must be in [1, 2^31) (got %lld)", entry, (long long)t.p);
+  if (t.ld < t.n)
+    return fail(DCOR_EINVAL, "%s: ld = %lld < n = %lld", entry, (long long)t.ld, (long long)t.n);
+  return DCOR_OK;
+}
+template <class T> int hrs_table_clips(const char* entry, const T& t) {
+  if ((uintptr_t)t.D & 7) return fail(DCOR_EINVAL, "%s: D must be aligned to 8 bytes", entry);
+  for (int64_t c = 0; c < t.p; ++c)
+    if (!std::isfinite(t.lam[c]) || !(t.lam[c] > 0.0))
+      return fail(DCOR_EINVAL, "%s: column %lld: lam must be finite and > 0 (got %g)", entry, (long long)c,
+                  t.lam[c]);
+  return DCOR_OK;
+}
+template <class T> int hrs_table_mix(const T& t) {
+  MixConst mx;
+  if (int st = check_common(t.n, 1.0, 1.0, t.alpha)) return st;
+  return make_mix(t.nsim, t.alpha, mx);
+}
+
 }  // namespace
 
 dcor_premat_subg hrs_segment_desc(const dcor_premat_subg& base, const dcor_hrs_segment& g) {
@@ -467,24 +493,13 @@ int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* se
     return fail(DCOR_EINVAL, "hrs_table: n must be in [2, %d] (got %lld): the kernel keeps a replicate's "
                 "u16 batch indices in LDS and there is no fallback for a larger table", DCOR_DICT_NMAX,
                 (long long)t->n);
-  if (t->p < 1 || t->p > 0x7fffffffLL)
-    return fail(DCOR_EINVAL, "hrs_table: p must be in [1, 2^31) (got %lld)", (long long)t->p);
-  if (t->ld < t->n)
-    return fail(DCOR_EINVAL, "hrs_table: ld = %lld < n = %lld", (long long)t->ld, (long long)t->n);
+  if (int st = hrs_table_shape("hrs_table", *t)) return st;
   if (!HrsTableLayout(0, 0, t->n, t->p).ok)
     return fail(DCOR_EINVAL, "hrs_table: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)",
                 (long long)t->p, (long long)t->n);
-  if ((uintptr_t)t->D & 7) return fail(DCOR_EINVAL, "hrs_table: D must be aligned to 8 bytes");
-  for (int64_t c = 0; c < t->p; ++c)
-    if (!std::isfinite(t->lam[c]) || !(t->lam[c] > 0.0))
-      return fail(DCOR_EINVAL, "hrs_table: column %lld: lam must be finite and > 0 (got %g)", (long long)c,
-                  t->lam[c]);
+  if (int st = hrs_table_clips("hrs_table", *t)) return st;
   if (!(t->delta > 0.0)) return fail(DCOR_EINVAL, "hrs_table: delta must be positive");
-  {  // alpha and nsim, as every segment's make_subg would refuse them
-    MixConst mx;
-    if (int st = check_common(t->n, 1.0, 1.0, t->alpha)) return st;
-    if (int st = make_mix(t->nsim, t->alpha, mx)) return st;
-  }
+  if (int st = hrs_table_mix(*t)) return st;
   if (int st = segment_heads("hrs_table", segs, nseg, t->p, items)) return st;
   // every segment's launch constants: those of the reference call on its pair, lam and eps
   int64_t first = 0;
@@ -504,6 +519,83 @@ int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* se
   }
   if (!HrsTableLayout(*items, (int64_t)tab.size(), t->n, t->p).ok)
     return fail(DCOR_EINVAL, "hrs_table: scratch bytes overflow (p = %lld, n = %lld)", (long long)t->p,
+                (long long)t->n);
+  return DCOR_OK;
+}
+
+int64_t hrs_pair_count(const uint64_t* valid, int64_t n, int64_t col_x, int64_t col_y) {
+  const int64_t nw = (n + 63) >> 6;
+  const uint64_t* a = valid + col_x * nw;
+  const uint64_t* b = valid + col_y * nw;
+  int64_t c = 0;
+  for (int64_t w = 0; w + 1 < nw; ++w) c += __builtin_popcountll(a[w] & b[w]);
+  const uint64_t tail = (n & 63) ? (~0ull >> (64 - (n & 63))) : ~0ull;   // the rows of the last word
+  return c + __builtin_popcountll(a[nw - 1] & b[nw - 1] & tail);
+}
+
+int plan_hrs_table_pairwise(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair_segment* segs,
+                            int64_t nseg, std::vector<HrsPairNaSegConst>& tab,
+                            std::vector<HrsPairSlot>& slots, PrematSubgConst* c0, int64_t* panel_elems,
+                            int64_t* items, int64_t* max_km) {
+  const char* const entry = "hrs_table_pairwise";
+  *items = 0; *max_km = 0; *panel_elems = 0;
+  if (!t->D || !t->lam || !t->valid) return fail(DCOR_EINVAL, "%s: null argument (D, lam, valid)", entry);
+  if (t->n < 2 || t->n > 0x7fffffffLL)
+    return fail(DCOR_EINVAL, "%s: n must be in [2, 2^31) (got %lld)", entry, (long long)t->n);
+  if (int st = hrs_table_shape(entry, *t)) return st;
+  if (!HrsPairTableLayout(0, 0, 0, t->n, t->p, 0).ok)
+    return fail(DCOR_EINVAL, "%s: p * ceil(n / 64) * 8 scratch bytes overflow (p = %lld, n = %lld)", entry,
+                (long long)t->p, (long long)t->n);
+  if (int st = hrs_table_clips(entry, *t)) return st;
+  if (!(t->delta > 0.0) && !std::isnan(t->delta))
+    return fail(DCOR_EINVAL, "%s: delta must be positive, or NaN for 1 / n_ab per pair", entry);
+  if (int st = hrs_table_mix(*t)) return st;
+  if (int st = segment_heads(entry, segs, nseg, t->p, items)) return st;
+  // every segment's pair, then its launch constants: those of the reference call on the pair's
+  // n_ab compacted rows, lam and eps
+  struct Pair { int64_t n_ab, slot; };   // slot: -1 until a segment with replicates names the pair
+  std::map<std::pair<int32_t, int32_t>, Pair> seen;
+  int64_t first = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_hrs_pair_segment& g = segs[i];
+    const auto at = seen.emplace(std::make_pair(g.col_x, g.col_y), Pair{0, -1});
+    Pair& pr = at.first->second;
+    if (at.second) pr.n_ab = hrs_pair_count(t->valid, t->n, g.col_x, g.col_y);
+    if (pr.n_ab < 2 || pr.n_ab > DCOR_DICT_NMAX)
+      return fail(DCOR_EINVAL, "%s: segment %lld: columns (%d, %d) have n_ab = %lld pairwise-complete rows, "
+                  "must be in [2, %d]: a replicate keeps u16 indices of the compacted rows in LDS", entry,
+                  (long long)i, (int)g.col_x, (int)g.col_y, (long long)pr.n_ab, DCOR_DICT_NMAX);
+    dcor_hrs_table_desc u;   // the reference call's table: the pair's own count and delta (rds:199)
+    std::memset(&u, 0, sizeof(u));
+    u.n = pr.n_ab; u.p = t->p; u.ld = t->ld; u.D = t->D; u.lam = t->lam;
+    u.alpha = t->alpha; u.delta = std::isnan(t->delta) ? 1.0 / (double)pr.n_ab : t->delta; u.nsim = t->nsim;
+    const dcor_premat_subg q = hrs_pair_desc(u, g);
+    PrematSubgConst pc;
+    if (int st = premat_subg_const(&q, pc)) return st;
+    if (g.reps == 0) continue;
+    if (tab.empty()) *c0 = pc;
+    if (pr.slot < 0) {   // a pair not run before: its panel follows the others'
+      HrsPairSlot sl;
+      std::memset(&sl, 0, sizeof(sl));
+      sl.n_ab = pr.n_ab; sl.panel = *panel_elems;
+      sl.col_x = g.col_x; sl.col_y = g.col_y;
+      *panel_elems += hrs_pair_panel_elems(pr.n_ab);
+      pr.slot = (int64_t)slots.size();
+      slots.push_back(sl);
+    }
+    HrsPairNaSegConst r;
+    std::memset(&r, 0, sizeof(r));
+    hrs_segment_record(pc, g, first, r);
+    r.col_x = g.col_x; r.col_y = g.col_y;
+    r.n = pc.s.n; r.nd = pc.s.nd; r.sqrt_n = pc.s.sqrt_n;
+    hrs_feistel_split(pc.s.n, &r.pa, &r.pc);
+    r.panel = slots[(size_t)pr.slot].panel;
+    first += g.reps;
+    tab.push_back(r);
+    *max_km = std::max(*max_km, pc.s.k * (int64_t)pc.s.m);
+  }
+  if (!HrsPairTableLayout(*items, (int64_t)tab.size(), (int64_t)slots.size(), t->n, t->p, *panel_elems).ok)
+    return fail(DCOR_EINVAL, "%s: scratch bytes overflow (p = %lld, n = %lld)", entry, (long long)t->p,
                 (long long)t->n);
   return DCOR_OK;
 }

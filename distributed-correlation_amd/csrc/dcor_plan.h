@@ -1,5 +1,5 @@
 // dcor_plan.h -- the host decisions that need no device: the error reporter, the argument checks,
-// every launch constant (R operation order, cited) and the segment planners of the seven
+// every launch constant (R operation order, cited) and the segment planners of the eight
 // segment-list entries.  Plain C++: neither this header nor dcor_plan.cpp includes the HIP
 // runtime, so the unit compiles, runs and is sanitized with a host compiler alone
 // (tests/host/plan_check.cpp).  Not part of the ABI.
@@ -119,6 +119,26 @@ dcor_premat_subg hrs_pair_desc(const dcor_hrs_table_desc& t, const dcor_hrs_pair
 // items: the call's replicates; max_km: the largest k m of the kept segments.
 int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs, int64_t nseg,
                    std::vector<HrsPairSegConst>& tab, int64_t* items, int64_t* max_km);
+
+// dcor_hrs_table_pairwise_launch.  The count of rows present in both columns: popcount of the ANDed
+// mask words (column c's nw = ceil(n / 64) words at valid + c * nw), the last word's bits at i >= n
+// masked off.
+int64_t hrs_pair_count(const uint64_t* valid, int64_t n, int64_t col_x, int64_t col_y);
+// Every check of the entry after its null checks of t, segs and d_out: plan_hrs_table's in its
+// order with the bound on n replaced by 2 <= n < 2^31, valid non-null beside D and lam, delta > 0 or
+// NaN; then per segment (one without replicates too) 2 <= n_ab <= DCOR_DICT_NMAX (the message names
+// the segment and n_ab) and its constants; then the whole scratch.  slots: the distinct ordered
+// pairs of the segments with replicates in order of first use, each with its n_ab and its panel's
+// first element (hrs_pair_panel_elems apart); panel_elems: the panels' double2 elements in all.
+// A kept segment's record holds, field for field, what plan_hrs_fused_sweep builds for
+// hrs_pair_desc at n = n_ab and delta = t->delta or 1 / n_ab, and n_ab, nd, sqrt_n (make_subg's),
+// the Feistel split of ceil(log2 n_ab) bits and its slot's panel.  c0: the first kept segment's
+// constants (the call-wide crit, mix and hrs are read from it; untouched when nothing is kept);
+// items, max_km: as plan_hrs_table's.
+int plan_hrs_table_pairwise(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair_segment* segs,
+                            int64_t nseg, std::vector<HrsPairNaSegConst>& tab,
+                            std::vector<HrsPairSlot>& slots, PrematSubgConst* c0, int64_t* panel_elems,
+                            int64_t* items, int64_t* max_km);
 
 // dcor_subg_panel_launch.  Every check of the entry after its null checks of p, segs and d_out, in
 // the header's order (X and Y, n, eta1 and eta2, alpha, nsim, then the segments' fields and ranges,

@@ -2037,8 +2037,9 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_fused_epilogue(PrematSubgCon
 // record equals the per-segment launch's bit for bit.  The table is read through the constant
 // address space at workgroup-uniform addresses: scalar loads into SGPRs, once per segment a
 // workgroup enters, never per lane and never inside the replicate's loops.
-// The table's record is HrsSegConst (the sweep) or HrsPairSegConst (the table entry, which adds the
-// segment's two columns): one load for both, the search and the cursor are dcor_segtab.h's.
+// The table's record is HrsSegConst (the sweep), HrsPairSegConst (the table entry, which adds the
+// segment's two columns) or HrsPairNaSegConst (the pairwise table entry, which adds the segment's
+// own n): one load for the shared fields, the search and the cursor are dcor_segtab.h's.
 
 // Segment s's constants over the sweep-wide ones in p, its keys into hk.
 template <class Seg>
@@ -2051,6 +2052,14 @@ __device__ __forceinline__ void hrs_seg_load(SegTab<Seg> tab, int s, PrematSubgC
   c.eps_r = tab[s].eps_r; p.crit_sqrt2_s = tab[s].crit_sqrt2_s;
   hk.ni0 = tab[s].ni0; hk.ni1 = tab[s].ni1; hk.in0 = tab[s].in0; hk.in1 = tab[s].in1;
   hk.rep_begin = tab[s].rep_begin;
+}
+// The pairwise table entry's record: what follows from the segment's own sample count as well (the
+// range of the permutation and of the local noise, the INT moments' divisor, the Feistel split).
+__device__ __forceinline__ void hrs_seg_load(SegTab<HrsPairNaSegConst> tab, int s, PrematSubgConst& p,
+                                             HrsKeys& hk) {
+  hrs_seg_load<HrsPairNaSegConst>(tab, s, p, hk);
+  p.s.n = tab[s].n; p.s.nd = tab[s].nd; p.s.sqrt_n = tab[s].sqrt_n;
+  hk.pa = tab[s].pa; hk.pc = tab[s].pc;
 }
 
 template <int WPE>
@@ -2171,6 +2180,104 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_table(PrematSubgConst p, i
   }
 }
 
+// ------------------------- the same on the pairwise-complete cases of a table with gaps ---
+// dcor_hrs_table_pairwise_launch: a pair's samples are the rows present in both of its columns
+// (real-data-sims.R:119-120, 187-189), so n differs from pair to pair and the preparation is per
+// pair: the pair's rows compacted into a packed panel, which k_hrs_pair_table gathers as
+// k_hrs_sweep_fused_l2 gathers k_premat_xy_pack's.
+
+// One workgroup per slot (a distinct ordered pair of the call): an order-preserving compaction of
+// the rows of ok = valid[col_x] & valid[col_y] into the slot's panel, the sample of rank r as
+// (rclip(D[col_x][i], lam[col_x]), rclip(D[col_y][i], lam[col_y])) -- k_premat_xy_pack's bits for
+// xyc and, X being the sender under one bound per column, for soc.  HRS_PACK_NT mask words (64 rows
+// each) per trip: a word's first rank is the running base plus the exclusive scan of the words'
+// popcounts (DPP within a wave, the wave totals through LDS), and row i of a word has rank first +
+// popcount(word & ((1 << (i & 63)) - 1)).  A rank has one writer: no atomics.  Rows at i >= n are
+// masked out of the last word, so D is read at present rows only; the host has checked the same
+// masks' count n_ab <= 65536, which bounds every rank.  The element after an odd n_ab is zero.
+#define HRS_PACK_NT 256
+__global__ __launch_bounds__(HRS_PACK_NT) void k_hrs_pair_pack(const double* __restrict__ D, int64_t ld,
+                                                               int64_t n, int64_t nw,
+                                                               const double* __restrict__ lam,
+                                                               const uint64_t* __restrict__ masks,
+                                                               const HrsPairSlot* __restrict__ slots,
+                                                               double2* __restrict__ panels) {
+  __shared__ uint64_t sw[HRS_PACK_NT];            // the trip's ANDed words
+  __shared__ uint32_t sp[HRS_PACK_NT];            // each word's first rank
+  __shared__ uint32_t wtot[HRS_PACK_NT / 64];
+  const HrsPairSlot sl = slots[blockIdx.x];
+  const double* __restrict__ xa = D + (int64_t)sl.col_x * ld;
+  const double* __restrict__ xb = D + (int64_t)sl.col_y * ld;
+  const uint64_t* __restrict__ ma = masks + (int64_t)sl.col_x * nw;
+  const uint64_t* __restrict__ mb = masks + (int64_t)sl.col_y * nw;
+  const double la = lam[sl.col_x], lb = lam[sl.col_y];
+  double2* __restrict__ dst = panels + sl.panel;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  uint32_t base = 0;
+  for (int64_t w0 = 0; w0 < nw; w0 += HRS_PACK_NT) {
+    const int64_t w = w0 + tid;
+    uint64_t ok = 0;
+    if (w < nw) {
+      ok = ma[w] & mb[w];
+      if (w == nw - 1 && (n & 63)) ok &= ~0ull >> (64 - (n & 63));
+    }
+    const uint32_t inc = wave_incl_scan_u32((uint32_t)__popcll(ok));
+    if (lane == 63) wtot[wv] = inc;
+    __syncthreads();   // the wave totals; the previous trip's readers of sw / sp are past it too
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int v = 0; v < HRS_PACK_NT / 64; ++v) {
+      before += v < wv ? wtot[v] : 0u;
+      total += wtot[v];
+    }
+    sw[tid] = ok;
+    sp[tid] = base + before + inc - (uint32_t)__popcll(ok);
+    base += total;
+    __syncthreads();
+    // the trip's rows, consecutive lanes on consecutive rows: thread tid takes the rows tid + 256 j,
+    // bit `lane` of word 4 j + wv (one LDS address per wave)
+    const int64_t row0 = w0 * 64;
+    for (int j = 0; j < 64 && row0 + (int64_t)j * HRS_PACK_NT < n; ++j) {
+      const int q = j * (HRS_PACK_NT / 64) + wv;
+      const uint64_t wd = sw[q];
+      if ((wd >> lane) & 1ull) {
+        const int64_t i = row0 + (int64_t)j * HRS_PACK_NT + tid;
+        const uint32_t r = sp[q] + (uint32_t)__popcll(wd & ((1ull << lane) - 1ull));
+        if ((int64_t)r < sl.n_ab) dst[r] = make_double2(rclip(xa[i], la), rclip(xb[i], lb));
+      }
+    }
+  }
+  if (tid == 0 && (sl.n_ab & 1)) dst[sl.n_ab] = make_double2(0.0, 0.0);
+}
+
+// k_hrs_table's persistent shell over the pairwise record: on entering a segment its n, nd, sqrt_n,
+// Feistel split and panel as well, all at a workgroup-uniform address, then the unchanged
+// hrs_fused_l2_item on the packed panel (one clip bound per column and X the sender: xy and so are
+// the same values).  A segment's n is workgroup-uniform, so every thread reaches both barriers of
+// the item.  gs holds the largest k m of the segments.
+template <int WPE>
+__global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_pair_table(PrematSubgConst p,
+                                                                const HrsPairNaSegConst* __restrict__ tab_g,
+                                                                int nseg, int64_t items,
+                                                                const double2* __restrict__ panels,
+                                                                SubgPartial* __restrict__ part) {
+  extern __shared__ double dsm[];
+  double* red = dsm;
+  uint16_t* gs = reinterpret_cast<uint16_t*>(dsm + 20 * DICT_NW);
+  const SegTab<HrsPairNaSegConst> tab = (SegTab<HrsPairNaSegConst>)tab_g;
+  HrsKeys hk{0, 0, 0, 0, 0, 0, 0};
+  SegCursor cur;
+  HrsPackedLoad ld{nullptr, nullptr};
+  int par = 0;
+  for (int64_t it = blockIdx.x; it < items; it += gridDim.x, par ^= 1) {
+    cur.seek(tab, nseg, items, it, [&](int s) {
+      hrs_seg_load(tab, s, p, hk);
+      ld.xyc = ld.soc = panels + tab[s].panel;
+    });
+    hrs_fused_l2_item(p, hk, hk.rep_begin + (uint32_t)(it - cur.first), ld, gs, red, par, part + it);
+  }
+}
+
 // ============================================================ launchers ===
 static inline int last_err() { return (int)hipGetLastError(); }
 
@@ -2192,13 +2299,6 @@ int persistent_grid(const void* kernel, int threads, size_t lds, int64_t items, 
   const int64_t slots = (int64_t)cus * (per_cu < 1 ? 1 : per_cu);
   *grid = items < slots ? items : slots;
   return 0;
-}
-
-// The Feistel split of ceil(log2 n) bits (launch_perm's).
-static void hrs_feistel_split(int64_t n, int* pa, int* pc) {
-  int bits = 1;
-  while ((1ll << bits) < n) ++bits;
-  *pa = bits / 2; *pc = bits - *pa;
 }
 
 // The HRS streaming kernels' waves-per-SIMD arm (DCOR_HRS_WPE: 6, or 4).
@@ -2310,6 +2410,26 @@ int launch_hrs_table(const PrematSubgConst& c, const double* D, int64_t p, int64
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c, pa, pc, tab,
                      nseg, items, (const double*)cols, npad, (SubgPartial*)part);
   hipLaunchKernelGGL(k_hrs_sweep_fused_epilogue<HrsPairSegConst>, dim3((unsigned)items), dim3(DCOR_BLOCK), 0,
+                     (hipStream_t)stream, c, tab, nseg, (const SubgPartial*)part, out);
+  return (int)hipGetLastError();
+}
+
+int launch_hrs_pair_table(const PrematSubgConst& c, const double* D, int64_t n, int64_t ld, const double* lam,
+                          const uint64_t* masks, int64_t nw, const HrsPairSlot* slots, int nslot,
+                          double2* panels, const HrsPairNaSegConst* tab, int nseg, int64_t items,
+                          int64_t max_km, void* part, dcor_rep_out* out, void* stream) {
+  if (items <= 0 || nseg <= 0 || nslot <= 0) return 0;
+  const int wsel = hrs_wpe();
+  const size_t lds = hrs_l2_lds_bytes(max_km);   // k_hrs_sweep_fused_l2's threads and LDS
+  typedef void (*PairK)(PrematSubgConst, const HrsPairNaSegConst*, int, int64_t, const double2*, SubgPartial*);
+  const PairK kern = wsel == 4 ? k_hrs_pair_table<4> : k_hrs_pair_table<6>;
+  int64_t grid = 0;
+  if (int e = persistent_grid((const void*)kern, DICT_NT, lds, items, &grid, kLdsDynMax)) return e;
+  hipLaunchKernelGGL(k_hrs_pair_pack, dim3((unsigned)nslot), dim3(HRS_PACK_NT), 0, (hipStream_t)stream, D, ld,
+                     n, nw, lam, masks, slots, panels);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c, tab, nseg, items,
+                     (const double2*)panels, (SubgPartial*)part);
+  hipLaunchKernelGGL(k_hrs_sweep_fused_epilogue<HrsPairNaSegConst>, dim3((unsigned)items), dim3(DCOR_BLOCK), 0,
                      (hipStream_t)stream, c, tab, nseg, (const SubgPartial*)part, out);
   return (int)hipGetLastError();
 }

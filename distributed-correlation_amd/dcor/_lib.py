@@ -147,6 +147,14 @@ class HrsPairSegment(C.Structure):
     _fields_ = HrsSegment._fields_ + [("col_x", C.c_int32), ("col_y", C.c_int32)]
 
 
+class HrsTableNaDesc(C.Structure):
+    """dcor_hrs_table_na_desc (include/dcor.h): dcor_hrs_table_desc and the columns' presence masks (a
+    HOST array of p x ceil(n / 64) words, bit i & 63 of word i >> 6 = row i present)."""
+    _fields_ = [("n", C.c_int64), ("p", C.c_int64), ("ld", C.c_int64), ("D", _P), ("lam", _D),
+                ("valid", C.POINTER(C.c_uint64)), ("alpha", C.c_double), ("delta", C.c_double),
+                ("nsim", C.c_int64)]
+
+
 class SubgTableDesc(C.Structure):
     """dcor_subg_table_desc (include/dcor.h): the shared table (p columns of n samples, ld apart), its
     per-column sub-Gaussian parameters (a HOST array of p doubles) and the call-wide settings."""
@@ -221,6 +229,8 @@ SIGNATURES = {
                                          _P, _P]),
     "dcor_hrs_table_launch": (C.c_int, [C.POINTER(HrsTableDesc), C.POINTER(HrsPairSegment), C.c_int64,
                                         _P, _P]),
+    "dcor_hrs_table_pairwise_launch": (C.c_int, [C.POINTER(HrsTableNaDesc), C.POINTER(HrsPairSegment),
+                                                 C.c_int64, _P, _P]),
     "dcor_subg_panel_launch": (C.c_int, [C.POINTER(SubgPanelDesc), C.POINTER(SubgSegment), C.c_int64,
                                          _P, _P]),
     "dcor_subg_table_launch": (C.c_int, [C.POINTER(SubgTableDesc), C.POINTER(SubgPairSegment), C.c_int64,

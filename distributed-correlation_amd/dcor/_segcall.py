@@ -1,5 +1,6 @@
 """The host side every segment-table entry shares (dcor_sign_panel_launch, dcor_sign_table_launch,
-dcor_subg_panel_launch, dcor_hrs_table_launch, dcor_subg_table_launch): the callers' segment tuples
+dcor_subg_panel_launch, dcor_hrs_table_launch, dcor_hrs_table_pairwise_launch,
+dcor_subg_table_launch): the callers' segment tuples
 packed as the entry's C records, and the call itself."""
 from __future__ import annotations
 

@@ -295,3 +295,13 @@ def hrs_table_distributed(Z, lam, segs, group=None, **kw):
     segs) byte for byte."""
     from . import hrs
     return _segments_distributed(lambda mine: hrs.table_segments(Z, lam, mine, **kw), segs, 5, 6, group)
+
+
+def hrs_table_pairwise_distributed(Z, lam, segs, group=None, **kw):
+    """dcor.hrs.pairwise_segments over G ranks, as hrs_table_distributed: each rank runs its pieces of
+    the flattened (segment, replicate) space in one native call and the records are all-gathered in
+    rank order.  A record depends only on (columns, masks, lam, eps, seeds, replicate), so the
+    [sum(reps), 6] result, identical on all ranks, equals one process's pairwise_segments(Z, lam,
+    segs) byte for byte."""
+    from . import hrs
+    return _segments_distributed(lambda mine: hrs.pairwise_segments(Z, lam, mine, **kw), segs, 5, 6, group)

@@ -368,13 +368,17 @@ def sweep_summaries(eps_grid, runs) -> dict:
 
 
 # ------------------------------------------------ every column pair of a shared table
-def standardize_table(raw, bounds, lap=None, rng=None):
+def standardize_table(raw, bounds, lap=None, rng=None, na="listwise"):
     """standardize_panel for the p columns of the (n, p) array raw with per-column clip intervals
     bounds[c] = (lo, hi): dp_sd, standardize_dp and lambda_from_priv per column
     (real-data-sims.R:273-287), then the rows with any NaN dropped (drop_na, :282).  lap: optional
     unit Laplace draws, [mean, m2] of column 0, of column 1, ...  Returns {"Z": (n', p) column-major,
-    "lam": [p], "priv": [p] {'mean', 'sd'}}."""
+    "lam": [p], "priv": [p] {'mean', 'sd'}}.  na='pairwise' keeps every row, NaN where a column has a
+    gap (dp_sd drops a column's own NA): the table of corr_matrix_pairwise, which drops per pair as
+    the estimators do (real-data-sims.R:119-120, 187-189)."""
     from . import api
+    if na not in ("listwise", "pairwise"):
+        raise ValueError("na must be 'listwise' or 'pairwise'")
     raw = np.asarray(raw, dtype=np.float64)
     if raw.ndim != 2 or raw.shape[1] < 1 or len(bounds) != raw.shape[1]:
         raise ValueError("raw must be an (n, p) array and bounds p (lo, hi) pairs")
@@ -388,7 +392,7 @@ def standardize_table(raw, bounds, lap=None, rng=None):
         priv.append(api.dp_sd(col, lo, hi, EPS_MEAN, EPS_M2, lap=lap[2 * c:2 * c + 2]))
         cols.append(api.standardize_dp(col, priv[c], lo, hi))
     Z = np.stack(cols, axis=1)
-    ok = ~np.isnan(Z).any(axis=1)
+    ok = ~np.isnan(Z).any(axis=1) if na == "listwise" else np.ones(len(Z), dtype=bool)
     lam = np.array([api.lambda_from_priv(lo, hi, pv) for (lo, hi), pv in zip(bounds, priv)], dtype=np.float64)
     return {"Z": np.asfortranarray(Z[ok]), "lam": lam, "priv": priv}
 
@@ -424,19 +428,41 @@ def table_segments(Z, lam, segs, nsim=2000, alpha=0.05, delta=None, stream=None)
     return run_segment_call(_lib.lib.dcor_hrs_table_launch, desc, arr, len(segs), total, stream)
 
 
+def _pairs_of(Z, pairs):
+    from .signpanel import _table, all_pairs
+    _, _, p = _table(Z)
+    return p, all_pairs(p) if pairs is None else [(int(a), int(b)) for a, b in pairs]
+
+
+def _corr_matrix(run, Z, eps, reps, pairs):
+    """corr_matrix / corr_matrix_pairwise: run(segs) -> [sum(reps), 6] is the table call."""
+    from .signpanel import _pair_matrices
+    p, pairs = _pairs_of(Z, pairs)
+    segs = [(a, b, eps, 10 + 1000 * (j + 1), 20 + 1000 * (j + 1), 0, reps) for j, (a, b) in enumerate(pairs)]
+    runs = run(segs).reshape(len(pairs), reps, 6)
+    return {"pairs": pairs, "runs": runs, **_pair_matrices(p, pairs, runs)}
+
+
+def _corr_matrix_sweep(run, Z, eps_grid, reps, pairs):
+    """corr_matrix_sweep / corr_matrix_sweep_pairwise: run(segs) -> [sum(reps), 6] is the table call."""
+    eps_grid = list(eps_grid)
+    _, pairs = _pairs_of(Z, pairs)
+    ne = len(eps_grid)
+    segs = [(a, b, e, 10 + 1000 * (j * ne + idx), 20 + 1000 * (j * ne + idx), 0, reps)
+            for j, (a, b) in enumerate(pairs) for idx, e in enumerate(eps_grid, start=1)]
+    runs = run(segs).reshape(len(pairs), ne, reps, 6)
+    return {"pairs": pairs, "eps": eps_grid, "runs": runs,
+            "summaries": [sweep_summaries(eps_grid, runs[j]) for j in range(len(pairs))]}
+
+
 def corr_matrix(Z, lam, eps, reps, pairs=None, nsim=2000, alpha=0.05, delta=None, stream=None):
     """The private correlation of every column pair of the standardised (n, p) table Z under the
     study's estimators at one eps: `reps` runs per pair in one native call.  pairs: every a < b in
     row-major order by default; pair j runs under the keys of corr_matrix_sweep with a one-eps grid,
     10 + 1000 (j + 1) and 20 + 1000 (j + 1).  Returns what dcor.signpanel.corr_matrix returns:
     {"pairs", "runs" [npairs, reps, 6], "ni", "int"}."""
-    from .signpanel import _pair_matrices, _table, all_pairs
-    _, _, p = _table(Z)
-    pairs = all_pairs(p) if pairs is None else [(int(a), int(b)) for a, b in pairs]
-    segs = [(a, b, eps, 10 + 1000 * (j + 1), 20 + 1000 * (j + 1), 0, reps) for j, (a, b) in enumerate(pairs)]
-    runs = table_segments(Z, lam, segs, nsim=nsim, alpha=alpha, delta=delta,
-                          stream=stream).reshape(len(pairs), reps, 6)
-    return {"pairs": pairs, "runs": runs, **_pair_matrices(p, pairs, runs)}
+    return _corr_matrix(lambda segs: table_segments(Z, lam, segs, nsim=nsim, alpha=alpha, delta=delta,
+                                                    stream=stream), Z, eps, reps, pairs)
 
 
 def corr_matrix_sweep(Z, lam, eps_grid=EPS_GRID, reps=R_PER_EPS, pairs=None, nsim=2000, alpha=0.05,
@@ -446,14 +472,84 @@ def corr_matrix_sweep(Z, lam, eps_grid=EPS_GRID, reps=R_PER_EPS, pairs=None, nsi
     10 + 1000 (j n_eps + idx) and 20 + 1000 (j n_eps + idx), so pair 0's part equals
     eps_sweep(mode='fused') on its columns.  Returns what dcor.signpanel.corr_matrix_sweep returns:
     {"pairs", "eps", "runs" [npairs, n_eps, reps, 6], "summaries"}."""
-    from .signpanel import _table, all_pairs
-    eps_grid = list(eps_grid)
-    _, _, p = _table(Z)
-    pairs = all_pairs(p) if pairs is None else [(int(a), int(b)) for a, b in pairs]
-    ne = len(eps_grid)
-    segs = [(a, b, e, 10 + 1000 * (j * ne + idx), 20 + 1000 * (j * ne + idx), 0, reps)
-            for j, (a, b) in enumerate(pairs) for idx, e in enumerate(eps_grid, start=1)]
-    runs = table_segments(Z, lam, segs, nsim=nsim, alpha=alpha, delta=delta,
-                          stream=stream).reshape(len(pairs), ne, reps, 6)
-    return {"pairs": pairs, "eps": eps_grid, "runs": runs,
-            "summaries": [sweep_summaries(eps_grid, runs[j]) for j in range(len(pairs))]}
+    return _corr_matrix_sweep(lambda segs: table_segments(Z, lam, segs, nsim=nsim, alpha=alpha, delta=delta,
+                                                          stream=stream), Z, eps_grid, reps, pairs)
+
+
+# ------------------------------- the same on pairwise-complete cases of a table with gaps
+def valid_mask(Z):
+    """The presence masks of the (n, p) table Z as dcor_hrs_table_pairwise_launch takes them: uint64
+    [p, ceil(n / 64)], bit (i & 63) of word [c, i >> 6] set when Z[i, c] is not NaN (little-endian
+    bit order); the last word's bits at i >= n are zero."""
+    Z = np.asarray(Z, dtype=np.float64)
+    if Z.ndim != 2 or Z.shape[0] < 1 or Z.shape[1] < 1:
+        raise ValueError("Z must be an (n, p) array with n, p >= 1")
+    n, p = Z.shape
+    bits = np.zeros((p, 64 * ((n + 63) // 64)), dtype=np.uint8)
+    bits[:, :n] = ~np.isnan(Z.T)
+    return np.packbits(bits, axis=1, bitorder="little").view("<u8").astype(np.uint64).reshape(p, -1)
+
+
+def _mask_rows(valid, n):
+    """valid [p, nw] -> bool [p, n]: the rows each column has."""
+    by = np.ascontiguousarray(valid).astype("<u8").view(np.uint8)
+    return np.unpackbits(by, axis=1, bitorder="little")[:, :n].astype(bool)
+
+
+def pairwise_segments(Z, lam, segs, nsim=2000, alpha=0.05, delta=None, valid=None, stream=None):
+    """table_segments on the pairwise-complete cases of a table with gaps, in one native call
+    (dcor_hrs_table_pairwise_launch): a segment on (col_x, col_y) runs on the n_ab rows present in
+    both columns, as the reference's estimators drop NA per pair (real-data-sims.R:119-120, 187-189).
+    Its records equal hrs_replicates(Z[ok, col_x], Z[ok, col_y], lam[col_x], lam[col_y], eps, reps,
+    seed_ni, seed_int, rep_begin=rep_begin, mode='fused') byte for byte, with the geometry and
+    delta_clip = 1 / n_ab (delta=None; :199) of that pair.  valid: the masks of valid_mask(Z) by
+    default (present = not NaN); the value of Z at a row its column's mask leaves out is never used.
+    Every named pair needs 2 <= n_ab <= 65536; n itself may be larger."""
+    import ctypes as C
+
+    from . import _lib
+    from ._segcall import pack_segments, run_segment_call
+    from .signpanel import _table
+    segs = list(segs)
+    F, n, p = _table(Z)
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    if lam.shape != (p,):
+        raise ValueError(f"lam must hold one clip bound per column ({p})")
+    valid = valid_mask(F) if valid is None else np.ascontiguousarray(valid, dtype=np.uint64)
+    if valid.shape != (p, (n + 63) // 64):
+        raise ValueError(f"valid must be uint64 [{p}, {(n + 63) // 64}]")
+    for a, b, *_ in segs:
+        if not (0 <= int(a) < p and 0 <= int(b) < p):
+            raise ValueError(f"columns ({a}, {b}) outside [0, {p})")
+    arr, total = pack_segments(_lib.HrsPairSegment, segs, 6)
+    import torch
+    Dd = torch.as_tensor(F.reshape(-1, order="F"), device="cuda")   # the one upload
+    desc = _lib.HrsTableNaDesc(n=n, p=p, ld=n, D=Dd.data_ptr(), lam=lam.ctypes.data_as(C.POINTER(C.c_double)),
+                               valid=valid.ctypes.data_as(C.POINTER(C.c_uint64)), alpha=float(alpha),
+                               delta=float("nan") if delta is None else float(delta), nsim=int(nsim))
+    return run_segment_call(_lib.lib.dcor_hrs_table_pairwise_launch, desc, arr, len(segs), total, stream)
+
+
+def _n_pair(Z, valid):
+    """[p, p] int64: the rows present in both columns (the diagonal: in the column itself)."""
+    Z = np.asarray(Z)
+    V = _mask_rows(valid_mask(Z) if valid is None else valid, Z.shape[0]).astype(np.int64)
+    return V @ V.T
+
+
+def corr_matrix_pairwise(Z, lam, eps, reps, pairs=None, nsim=2000, alpha=0.05, delta=None, valid=None,
+                         stream=None):
+    """corr_matrix with every pair on its own pairwise-complete rows (pairwise_segments): the same
+    pairs, keys and result, and "n_pair", the [p, p] integer matrix of the pairs' counts n_ab."""
+    run = lambda segs: pairwise_segments(Z, lam, segs, nsim=nsim, alpha=alpha, delta=delta, valid=valid,
+                                         stream=stream)
+    return {**_corr_matrix(run, Z, eps, reps, pairs), "n_pair": _n_pair(Z, valid)}
+
+
+def corr_matrix_sweep_pairwise(Z, lam, eps_grid=EPS_GRID, reps=R_PER_EPS, pairs=None, nsim=2000, alpha=0.05,
+                               delta=None, valid=None, stream=None):
+    """corr_matrix_sweep with every pair on its own pairwise-complete rows (pairwise_segments): the
+    same pairs, keys and result, and "n_pair", the [p, p] integer matrix of the pairs' counts n_ab."""
+    run = lambda segs: pairwise_segments(Z, lam, segs, nsim=nsim, alpha=alpha, delta=delta, valid=valid,
+                                         stream=stream)
+    return {**_corr_matrix_sweep(run, Z, eps_grid, reps, pairs), "n_pair": _n_pair(Z, valid)}

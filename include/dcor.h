@@ -514,6 +514,48 @@ typedef struct dcor_hrs_pair_segment {
 int dcor_hrs_table_launch(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs,
                           int64_t nseg, dcor_rep_out* d_out, void* stream);
 
+/* dcor_hrs_table_launch on the pairwise-complete cases of a table with gaps: the reference's HRS
+ * estimators start with ok <- !(is.na(X) | is.na(Y)) (real-data-sims.R:119-120 for
+ * correlation_NI_subG, :187-189 for ci_INT_subG) and take n, the batch geometry, delta_clip = 1 / n
+ * (:199) and lambda_receiver_from_noise from that pair's own count.  valid holds one presence mask
+ * per column.  For a segment on (col_x, col_y) let ok = valid[col_x] & valid[col_y] and n_ab =
+ * popcount(ok): the segment's records equal, byte for byte, the records of
+ * dcor_hrs_fused_sweep_launch on a panel created on X = D[col_x][ok], Y = D[col_y][ok], the rows of
+ * ok in row order, with lam_x = lam_s = lam[col_x], lam_y = lam_o = lam[col_y], delta = the
+ * descriptor's delta or 1 / n_ab when that is NaN, and the same alpha, nsim, eps, seeds, rep_begin
+ * and reps: the same draw sites, the HRS geometry at n_ab (k < 2: k = 2, m = floor(n_ab / 2)) and
+ * the Feistel split of ceil(log2 n_ab) bits.  The value of D at a row that is not in ok is never
+ * used (NaN or anything else); a NaN at a row in ok reaches only the pairs that name its column.
+ * With every mask bit set and delta = 1 / n the call equals dcor_hrs_table_launch byte for byte.
+ * Records depend only on (columns, masks, lam, eps, seeds, replicate), never on the segment split,
+ * the order of segments or out_row.  One preparation launch (one workgroup per distinct ordered
+ * pair of the call: the pair's present rows compacted in order into a packed panel of clipped (x, y)
+ * samples, the bits k_premat_xy_pack forms), one streaming launch and one epilogue launch cover
+ * every pair and eps; a segment's constants, n_ab and what follows from it included, come from a
+ * device table.
+ * Checks, all on the host (which holds the masks and so knows every n_ab) before anything is
+ * enqueued and before any device access (an invalid call returns its code and leaves d_out
+ * untouched): those of dcor_hrs_table_launch with its bound on n replaced by 2 <= n < 2^31;
+ * non-null valid; delta > 0 or NaN; every named pair 2 <= n_ab <= 65536 (a replicate keeps u16
+ * indices of compacted positions in LDS, so n_ab is bounded and n is not), else DCOR_EINVAL with
+ * dcor_last_error naming the segment and n_ab; scratch bytes representable.  nseg == 0 or no
+ * replicates at all returns DCOR_OK with no device work.  Asynchronous on `stream`, no host
+ * synchronisation; scratch is stream-ordered (80 B per replicate, the segment and pair tables, 8 B
+ * per column, the masks, 16 B per present row of every distinct pair).  DCOR_HRS_WPE acts as in
+ * dcor_hrs_fused_launch.  D, lam, valid and segs are borrowed for the call only (D until the call's
+ * work on `stream` has run). */
+typedef struct dcor_hrs_table_na_desc {
+  int64_t n, p, ld;         /* rows per column, columns, elements between column starts */
+  const double* D;          /* DEVICE, column c = D + c * ld; borrowed for the call */
+  const double* lam;        /* HOST, [p]: column c's clip bound, finite and > 0 */
+  const uint64_t* valid;    /* HOST, [p][nw], nw = ceil(n / 64): bit (i & 63) of word c * nw + (i >> 6)
+                               set = row i of column c is present; bits at i >= n are ignored */
+  double alpha, delta;      /* delta > 0, or NaN: 1 / n_ab per pair (real-data-sims.R:199) */
+  int64_t nsim;
+} dcor_hrs_table_na_desc;
+int dcor_hrs_table_pairwise_launch(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair_segment* segs,
+                                   int64_t nseg, dcor_rep_out* d_out, void* stream);
+
 /* The sub-Gaussian estimators of the simulation (correlation_NI_subG + ci_INT_subG,
  * ver-cor-subG.R:25-108: contiguous batches, lambda_n / lambda_INT_n, any (eps1, eps2), either
  * sender) on the caller's own (X, Y), prepared once and shared by every replicate, with every noise
