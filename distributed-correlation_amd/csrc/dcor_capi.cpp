@@ -826,7 +826,7 @@ static int premat_subg_run(const dcor_premat_subg* d, const dcor_panel* panel, d
     void* q = lay.coded_base(part);
     p.dict_codes = lay.coded.codes(q);
     p.dict_vals = lay.coded.dict(q);
-    p.dict_ok = lay.coded.ok(q);
+    p.dict_ok = lay.coded.ok_flag(q);
   } else if (panel != nullptr && p.perm && panel->coded) {
     p.dict_codes = panel->codes();
     p.dict_vals = panel->dict();
@@ -1038,20 +1038,6 @@ int dcor_hrs_sweep_launch(const dcor_premat_subg* base, const dcor_panel* panel,
   });
 }
 
-// Fused sweep scratch: partials (one SubgPartial per replicate of the call) | the segment table |
-// pack (xyc | soc, uncoded panel).  Every region starts 256-B aligned when the base is.
-struct FusedSweepLayout {
-  int64_t n;
-  size_t tab_off, pack_off, bytes;
-  FusedSweepLayout(int64_t items, int64_t nseg, int64_t n_, bool pack)
-      : n(n_), tab_off(al256((size_t)items * sizeof(SubgPartial))),
-        pack_off(tab_off + al256((size_t)nseg * sizeof(HrsSegConst))),
-        bytes(pack_off + (pack ? (size_t)n_ * 2 * sizeof(double2) : 0)) {}
-  HrsSegConst* tab(void* base) const { return (HrsSegConst*)((char*)base + tab_off); }
-  double2* xyc(void* base) const { return (double2*)((char*)base + pack_off); }
-  double2* soc(void* base) const { return xyc(base) + n; }
-};
-
 int dcor_hrs_fused_sweep_launch(const dcor_premat_subg* base, const dcor_panel* panel,
                                 const dcor_hrs_segment* segs, int64_t nseg, dcor_rep_out* d_out,
                                 void* stream) {
@@ -1093,84 +1079,66 @@ static int seg_args(const char* entry, const void* desc, const void* segs, int64
   return DCOR_OK;
 }
 
+// The six table entries: the argument check, the planner, the device, one launch over the plan.
 int dcor_sign_panel_launch(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream) {
   if (int st = seg_args("sign_panel", p, segs, nseg, d_out)) return st;
-  if (nseg == 0) return DCOR_OK;   // nothing to run
-  std::vector<SignSegConst> tab;
-  int64_t items = 0;
-  if (int st = plan_sign_panel(p, segs, nseg, tab, &items)) return st;
-  if (items == 0) return DCOR_OK;
+  if (nseg == 0) return DCOR_OK;
+  SignPanelPlan plan;
+  if (int st = plan_sign_panel(p, segs, nseg, plan)) return st;
+  if (plan.items == 0) return DCOR_OK;
   if (int st = need_device()) return st;
-  const SignPanelLayout lay((int64_t)tab.size(), p->n);
-  return with_table("sign_panel", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
-    return launch_sign_panel(tab[0].s, p->X, p->Y, lay.means(buf), lay.xyc(buf), lay.tab(buf),
-                             (int)tab.size(), items, d_out, stream);
+  const SignPanelLayout& lay = plan.lay;
+  return with_table("sign_panel", lay.bytes, plan.tab, lay.tab_off, stream, [&](void* buf) {
+    return launch_sign_panel(plan.tab[0].s, p->X, p->Y, lay.means(buf), lay.xyc(buf), lay.tab(buf),
+                             (int)plan.tab.size(), plan.items, d_out, stream);
   });
 }
 
 int dcor_sign_table_launch(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream) {
   if (int st = seg_args("sign_table", t, segs, nseg, d_out)) return st;
-  if (nseg == 0) return DCOR_OK;   // nothing to run
-  std::vector<SignPairSegConst> tab;
-  int64_t items = 0;
-  if (int st = plan_sign_table(t, segs, nseg, tab, &items)) return st;
-  if (items == 0) return DCOR_OK;
+  if (nseg == 0) return DCOR_OK;
+  SignTablePlan plan;
+  if (int st = plan_sign_table(t, segs, nseg, plan)) return st;
+  if (plan.items == 0) return DCOR_OK;
   if (int st = need_device()) return st;
-  const SignTableLayout lay((int64_t)tab.size(), t->n, t->p);
-  return with_table("sign_table", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
-    return launch_sign_table(tab[0].s, t->D, t->p, t->ld, lay.means(buf), lay.cols(buf), lay.tab(buf),
-                             (int)tab.size(), items, d_out, stream);
+  const SignTableLayout& lay = plan.lay;
+  return with_table("sign_table", lay.bytes, plan.tab, lay.tab_off, stream, [&](void* buf) {
+    return launch_sign_table(plan.tab[0].s, t->D, t->p, t->ld, lay.means(buf), lay.cols(buf), lay.tab(buf),
+                             (int)plan.tab.size(), plan.items, d_out, stream);
   });
 }
 
 int dcor_hrs_table_launch(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs,
                           int64_t nseg, dcor_rep_out* d_out, void* stream) {
   if (int st = seg_args("hrs_table", t, segs, nseg, d_out)) return st;
-  if (nseg == 0) return DCOR_OK;   // nothing to run
-  std::vector<HrsPairSegConst> tab;
-  int64_t items = 0, max_km = 0;
-  if (int st = plan_hrs_table(t, segs, nseg, tab, &items, &max_km)) return st;
-  if (items == 0) return DCOR_OK;
+  if (nseg == 0) return DCOR_OK;
+  HrsTablePlan plan;
+  if (int st = plan_hrs_table(t, segs, nseg, plan)) return st;
+  if (plan.items == 0) return DCOR_OK;
   if (int st = need_device()) return st;
-  // the call-wide constants (n, nd, sqrt_n, crit, mix, hrs) from the first kept segment's reference
-  // call; everything that depends on lam or eps is read from the table
-  PrematSubgConst p;
-  for (int64_t i = 0; i < nseg; ++i) {
-    if (segs[i].reps == 0) continue;
-    const dcor_premat_subg q = hrs_pair_desc(*t, segs[i]);
-    if (int st = premat_subg_const(&q, p)) return st;
-    break;
-  }
-  p.X = p.Y = nullptr;
-  const HrsTableLayout lay(items, (int64_t)tab.size(), t->n, t->p);
-  return with_table("hrs_table", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
-    return launch_hrs_table(p, t->D, t->p, t->ld, lay.lam(buf), lay.cols(buf), lay.npad, lay.tab(buf),
-                            (int)tab.size(), items, max_km, buf, d_out, stream);
+  const HrsTableLayout& lay = plan.lay;
+  return with_table("hrs_table", lay.bytes, plan.tab, lay.tab_off, stream, [&](void* buf) {
+    return launch_hrs_table(plan.c0, t->D, t->p, t->ld, lay.lam(buf), lay.cols(buf), lay.npad, lay.tab(buf),
+                            (int)plan.tab.size(), plan.items, plan.max_km, buf, d_out, stream);
   }, false, {{lay.lam_off, t->lam, (size_t)t->p * sizeof(double)}});
 }
 
 int dcor_hrs_table_pairwise_launch(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair_segment* segs,
                                    int64_t nseg, dcor_rep_out* d_out, void* stream) {
   if (int st = seg_args("hrs_table_pairwise", t, segs, nseg, d_out)) return st;
-  if (nseg == 0) return DCOR_OK;   // nothing to run
-  std::vector<HrsPairNaSegConst> tab;
-  std::vector<HrsPairSlot> slots;
-  int64_t items = 0, max_km = 0, panel_elems = 0;
-  // p: the first kept segment's constants; the call-wide ones (crit, mix, hrs) are read from it,
-  // everything that depends on lam, eps or the pair's own count from the table
-  PrematSubgConst p;
-  if (int st = plan_hrs_table_pairwise(t, segs, nseg, tab, slots, &p, &panel_elems, &items, &max_km)) return st;
-  if (items == 0) return DCOR_OK;
+  if (nseg == 0) return DCOR_OK;
+  HrsPairTablePlan plan;
+  if (int st = plan_hrs_table_pairwise(t, segs, nseg, plan)) return st;
+  if (plan.items == 0) return DCOR_OK;
   if (int st = need_device()) return st;
-  p.X = p.Y = nullptr;
-  const HrsPairTableLayout lay(items, (int64_t)tab.size(), (int64_t)slots.size(), t->n, t->p, panel_elems);
-  return with_table("hrs_table_pairwise", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
-    return launch_hrs_pair_table(p, t->D, t->n, t->ld, lay.lam(buf), lay.masks(buf), lay.nw, lay.slots(buf),
-                                 (int)slots.size(), lay.panels(buf), lay.tab(buf), (int)tab.size(), items,
-                                 max_km, buf, d_out, stream);
-  }, false, {{lay.slot_off, slots.data(), slots.size() * sizeof(HrsPairSlot)},
+  const HrsPairTableLayout& lay = plan.lay;
+  return with_table("hrs_table_pairwise", lay.bytes, plan.tab, lay.tab_off, stream, [&](void* buf) {
+    return launch_hrs_pair_table(plan.c0, t->D, t->n, t->ld, lay.lam(buf), lay.masks(buf), lay.nw,
+                                 lay.slots(buf), (int)plan.slots.size(), lay.panels(buf), lay.tab(buf),
+                                 (int)plan.tab.size(), plan.items, plan.max_km, buf, d_out, stream);
+  }, false, {{lay.slot_off, plan.slots.data(), plan.slots.size() * sizeof(HrsPairSlot)},
              {lay.lam_off, t->lam, (size_t)t->p * sizeof(double)},
              {lay.mask_off, t->valid, (size_t)t->p * (size_t)lay.nw * sizeof(uint64_t)}});
 }
@@ -1178,42 +1146,33 @@ int dcor_hrs_table_pairwise_launch(const dcor_hrs_table_na_desc* t, const dcor_h
 int dcor_subg_panel_launch(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream) {
   if (int st = seg_args("subg_panel", p, segs, nseg, d_out)) return st;
-  if (nseg == 0) return DCOR_OK;   // nothing to run
-  std::vector<SubgSegConst> tab;
-  std::vector<SubgMeanSlot> slots;
-  SubgConst c0;
-  int64_t items = 0;
-  if (int st = plan_subg_panel(p, segs, nseg, tab, slots, &c0, &items)) return st;
-  if (items == 0) return DCOR_OK;
+  if (nseg == 0) return DCOR_OK;
+  SubgPanelPlan plan;
+  if (int st = plan_subg_panel(p, segs, nseg, plan)) return st;
+  if (plan.items == 0) return DCOR_OK;
   if (int st = need_device()) return st;
-  const int64_t nmeans = slots.back().off + slots.back().k;
-  const SubgPanelLayout lay((int64_t)tab.size(), (int64_t)slots.size(), nmeans, p->n);
-  return with_table("subg_panel", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
-    return launch_subg_panel(c0, p->X, p->Y, lay.slots(buf), (int)slots.size(), lay.means(buf), lay.xy(buf),
-                             lay.npad, lay.tab(buf), (int)tab.size(), items, d_out, stream);
-  }, false, {{lay.slot_off, slots.data(), slots.size() * sizeof(SubgMeanSlot)}});
+  const SubgPanelLayout& lay = plan.lay;
+  return with_table("subg_panel", lay.bytes, plan.tab, lay.tab_off, stream, [&](void* buf) {
+    return launch_subg_panel(plan.c0, p->X, p->Y, lay.slots(buf), (int)plan.slots.size(), lay.means(buf),
+                             lay.xy(buf), lay.npad, lay.tab(buf), (int)plan.tab.size(), plan.items, d_out, stream);
+  }, false, {{lay.slot_off, plan.slots.data(), plan.slots.size() * sizeof(SubgMeanSlot)}});
 }
 
 int dcor_subg_table_launch(const dcor_subg_table_desc* t, const dcor_subg_pair_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream) {
   if (int st = seg_args("subg_table", t, segs, nseg, d_out)) return st;
-  if (nseg == 0) return DCOR_OK;   // nothing to run
-  std::vector<SubgPairSegConst> tab;
-  std::vector<SubgMeanSlot> slots;
-  std::vector<double> clips;
-  SubgConst c0;
-  int64_t items = 0;
-  if (int st = plan_subg_table(t, segs, nseg, tab, slots, clips, &c0, &items)) return st;
-  if (items == 0) return DCOR_OK;
+  if (nseg == 0) return DCOR_OK;
+  SubgTablePlan plan;
+  if (int st = plan_subg_table(t, segs, nseg, plan)) return st;
+  if (plan.items == 0) return DCOR_OK;
   if (int st = need_device()) return st;
-  const int64_t nmeans = slots.back().off + slots.back().k;
-  const SubgTableLayout lay((int64_t)tab.size(), (int64_t)slots.size(), nmeans, t->n, t->p);
-  return with_table("subg_table", lay.bytes, tab, lay.tab_off, stream, [&](void* buf) {
-    return launch_subg_table(c0, t->D, t->p, t->ld, lay.clips(buf), lay.slots(buf), (int)slots.size(),
-                             lay.means(buf), lay.mpitch, lay.cols(buf), lay.npad, lay.tab(buf), (int)tab.size(),
-                             items, d_out, stream);
-  }, false, {{lay.slot_off, slots.data(), slots.size() * sizeof(SubgMeanSlot)},
-             {lay.clip_off, clips.data(), clips.size() * sizeof(double)}});
+  const SubgTableLayout& lay = plan.lay;
+  return with_table("subg_table", lay.bytes, plan.tab, lay.tab_off, stream, [&](void* buf) {
+    return launch_subg_table(plan.c0, t->D, t->p, t->ld, lay.clips(buf), lay.slots(buf), (int)plan.slots.size(),
+                             lay.means(buf), lay.mpitch, lay.cols(buf), lay.npad, lay.tab(buf),
+                             (int)plan.tab.size(), plan.items, d_out, stream);
+  }, false, {{lay.slot_off, plan.slots.data(), plan.slots.size() * sizeof(SubgMeanSlot)},
+             {lay.clip_off, plan.clips.data(), plan.clips.size() * sizeof(double)}});
 }
 
 int dcor_panel_dict_probe(const double* d_X, const double* d_Y, int64_t n, int* ok) {
@@ -1224,7 +1183,7 @@ int dcor_panel_dict_probe(const double* d_X, const double* d_Y, int64_t n, int* 
   DevBuf buf;
   const CodedPanelLayout lay(n);
   HIPCHK(buf.alloc(lay.bytes));
-  int* d_ok = lay.ok(buf.p);
+  int* d_ok = lay.ok_flag(buf.p);
   const int rc = launch_panel_dict(d_X, d_Y, n, lay.codes(buf.p), lay.dict(buf.p), d_ok, nullptr);
   if (rc) return hip_fail((hipError_t)rc, "panel_dict launch");
   HIPCHK(hipMemcpy(ok, d_ok, sizeof(int), hipMemcpyDeviceToHost));

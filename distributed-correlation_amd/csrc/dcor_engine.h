@@ -49,9 +49,6 @@ Variant variant(const char* name);
 constexpr int kLdsDynMax = 150 * 1024;
 constexpr int kLdsTiledMax = 160 * 1024;
 
-// Every scratch region on the panel / HRS path starts on a 256-B boundary.
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct DgpConst {
   int32_t dgp;
   int32_t nan_dgp;                      // gen_bounded_factor with rho outside [0, 1]: sqrt(3 rho)
@@ -160,38 +157,6 @@ struct PrematSubgConst {
 // A streaming kernel's sums of one replicate (slice) on their way to the epilogue.
 struct SubgPartial { double s[10]; };  // sP, sT, sT2, sU, sU2 as (hi, lo)
 static_assert(sizeof(SubgPartial) == 80, "scratch sizes and the kernels' partial stride");
-
-// ---- scratch layouts of the panel / HRS path: each the single definition of its buffer ----
-// Offsets and the total from the geometry, pointers over a base address.  Every region starts
-// 256-B aligned when the base is.
-// Coded panel: codes (n u16) | dict (2 columns x 256 doubles) | ok (one int in a 256-B tail).
-struct CodedPanelLayout {
-  size_t dict_off = 0, ok_off = 0, bytes = 0;
-  CodedPanelLayout() = default;
-  explicit CodedPanelLayout(int64_t n)
-      : dict_off(al256((size_t)n * 2)), ok_off(dict_off + 2 * 256 * sizeof(double)), bytes(ok_off + 256) {}
-  uint16_t* codes(void* base) const { return (uint16_t*)base; }
-  double* dict(void* base) const { return (double*)((char*)base + dict_off); }
-  int* ok(void* base) const { return (int*)((char*)base + ok_off); }
-};
-// Premat sub-G scratch: partials (one SubgPartial per replicate slice) | pack (xyc | soc: two
-// double2 per sample, uncoded shared panel) | a coded panel built per launch (dict).
-struct PrematScratchLayout {
-  int64_t n = 0;
-  size_t pack_off = 0, coded_off = 0, bytes = 0;
-  CodedPanelLayout coded;
-  PrematScratchLayout(int64_t reps, int64_t slices, int64_t n_, bool pack, bool dict)
-      : n(n_), pack_off(al256((size_t)reps * sizeof(SubgPartial) * slices)),
-        coded_off(pack_off + (pack ? (size_t)n_ * 2 * sizeof(double2) : 0)),
-        coded(dict ? CodedPanelLayout(n_) : CodedPanelLayout()) {
-    bytes = coded_off + coded.bytes;
-  }
-  // the partials from replicate slice `item` on
-  void* partials(void* base, int64_t item = 0) const { return (SubgPartial*)base + item; }
-  double2* xyc(void* base) const { return (double2*)((char*)base + pack_off); }
-  double2* soc(void* base) const { return xyc(base) + n; }
-  void* coded_base(void* base) const { return (char*)base + coded_off; }
-};
 
 size_t premat_dict_lds_bytes(int64_t n);
 // codes: n u16 (16-B padded), dict: 512 doubles, ok: 1 int (device).
@@ -359,31 +324,6 @@ struct HrsPairSegConst : HrsSegConst {
   int32_t col_x, col_y;
 };
 static_assert(sizeof(HrsPairSegConst) == 168, "the table entry's device table stride");
-// HRS-table scratch: partials (one SubgPartial per replicate of the call) | the segment table |
-// the p clip bounds | the p clipped columns as plain doubles, each zero-padded to npad = n rounded
-// up to 4, so every column starts 32-B aligned.  Every region starts 256-B aligned when the base
-// is.  ok is false when p * npad * 8 bytes (or the total) is not representable.
-struct HrsTableLayout {
-  int64_t npad;
-  size_t tab_off = 0, lam_off = 0, cols_off = 0, bytes = 0;
-  bool ok = false;
-  HrsTableLayout(int64_t items, int64_t nseg, int64_t n, int64_t p) : npad((n + 3) & ~(int64_t)3) {
-    const size_t lim = SIZE_MAX / 2;
-    if (n < 1 || p < 1 || nseg < 0 || items < 0 || (size_t)p > lim / 16 ||
-        (size_t)nseg > lim / (2 * sizeof(HrsPairSegConst)) || (size_t)items > lim / (2 * sizeof(SubgPartial)))
-      return;
-    tab_off = al256((size_t)items * sizeof(SubgPartial));
-    lam_off = tab_off + al256((size_t)nseg * sizeof(HrsPairSegConst));
-    cols_off = lam_off + al256((size_t)p * sizeof(double));
-    const size_t col_bytes = (size_t)npad * sizeof(double);
-    if (cols_off > lim || (size_t)p > (lim - cols_off) / col_bytes) return;
-    bytes = cols_off + (size_t)p * col_bytes;
-    ok = true;
-  }
-  HrsPairSegConst* tab(void* base) const { return (HrsPairSegConst*)((char*)base + tab_off); }
-  double* lam(void* base) const { return (double*)((char*)base + lam_off); }
-  double* cols(void* base) const { return (double*)((char*)base + cols_off); }
-};
 // The preparation launch (one workgroup per column of D: column c clipped at +-lam[c] with
 // k_premat_xy_pack's rclip, stored at pitch npad) and the streaming and epilogue launches over
 // `items` replicates of the nseg >= 1 segments in `tab` (device), as launch_hrs_fused_sweep.
@@ -424,38 +364,6 @@ struct HrsPairSlot {
 static_assert(sizeof(HrsPairSlot) == 24, "the pairwise table entry's slot table stride");
 // double2 elements a slot's panel takes
 __host__ __device__ inline int64_t hrs_pair_panel_elems(int64_t n_ab) { return (n_ab + 15) & ~(int64_t)15; }
-// Pairwise HRS-table scratch: partials (one SubgPartial per replicate of the call) | the segment
-// table, then the slot table | the p clip bounds | the p masks of nw = ceil(n / 64) words | the
-// slots' packed panels (panel_elems double2 in all).  Every region starts 256-B aligned when the base
-// is.  ok is false when the total is not representable.
-struct HrsPairTableLayout {
-  int64_t nw;
-  size_t tab_off = 0, slot_off = 0, lam_off = 0, mask_off = 0, panel_off = 0, bytes = 0;
-  bool ok = false;
-  HrsPairTableLayout(int64_t items, int64_t nseg, int64_t nslot, int64_t n, int64_t p, int64_t panel_elems)
-      : nw((n + 63) >> 6) {
-    const size_t lim = SIZE_MAX / 2;
-    if (n < 1 || p < 1 || nseg < 0 || nslot < 0 || items < 0 || panel_elems < 0 || (size_t)p > lim / 16 ||
-        (size_t)nseg > lim / (2 * sizeof(HrsPairNaSegConst)) || (size_t)nslot > lim / (2 * sizeof(HrsPairSlot)) ||
-        (size_t)items > lim / (2 * sizeof(SubgPartial)) || (size_t)panel_elems > lim / (2 * sizeof(double2)))
-      return;
-    tab_off = al256((size_t)items * sizeof(SubgPartial));
-    slot_off = tab_off + al256((size_t)nseg * sizeof(HrsPairNaSegConst));
-    lam_off = slot_off + al256((size_t)nslot * sizeof(HrsPairSlot));
-    mask_off = lam_off + al256((size_t)p * sizeof(double));
-    const size_t col_bytes = (size_t)nw * sizeof(uint64_t);
-    if (mask_off > lim || (size_t)p > (lim - mask_off) / col_bytes) return;
-    panel_off = mask_off + al256((size_t)p * col_bytes);
-    if (panel_off > lim || (size_t)panel_elems * sizeof(double2) > lim - panel_off) return;
-    bytes = panel_off + (size_t)panel_elems * sizeof(double2);
-    ok = true;
-  }
-  HrsPairNaSegConst* tab(void* base) const { return (HrsPairNaSegConst*)((char*)base + tab_off); }
-  HrsPairSlot* slots(void* base) const { return (HrsPairSlot*)((char*)base + slot_off); }
-  double* lam(void* base) const { return (double*)((char*)base + lam_off); }
-  uint64_t* masks(void* base) const { return (uint64_t*)((char*)base + mask_off); }
-  double2* panels(void* base) const { return (double2*)((char*)base + panel_off); }
-};
 // The preparation launch (one workgroup per slot: the rows of valid[col_x] & valid[col_y] compacted
 // in order into the slot's panel, sample r = (rclip(D[col_x][i], lam[col_x]), rclip(D[col_y][i],
 // lam[col_y])), k_premat_xy_pack's bits) and the streaming and epilogue launches over `items`
@@ -494,23 +402,6 @@ struct SubgMeanSlot {
   double md, inv_md;
 };
 static_assert(sizeof(SubgMeanSlot) == 40, "the sub-G panel's slot table stride");
-// Sub-G panel scratch: the segment table | the slot table | the batch means of every slot (16 B
-// per batch) | the packed panel (x, y) of n rounded up to npad (a multiple of 4; zeros from n on).
-// Every region starts 256-B aligned when the base is.  nmeans: the sum of the slots' k.
-struct SubgPanelLayout {
-  int64_t npad;
-  size_t tab_off = 0, slot_off, means_off, pack_off, bytes;
-  SubgPanelLayout(int64_t nseg, int64_t nslots, int64_t nmeans, int64_t n)
-      : npad((n + 3) & ~(int64_t)3),
-        slot_off(al256((size_t)nseg * sizeof(SubgSegConst))),
-        means_off(slot_off + al256((size_t)nslots * sizeof(SubgMeanSlot))),
-        pack_off(means_off + al256((size_t)nmeans * sizeof(double2))),
-        bytes(pack_off + (size_t)npad * sizeof(double2)) {}
-  SubgSegConst* tab(void* base) const { return (SubgSegConst*)((char*)base + tab_off); }
-  SubgMeanSlot* slots(void* base) const { return (SubgMeanSlot*)((char*)base + slot_off); }
-  double2* means(void* base) const { return (double2*)((char*)base + means_off); }
-  double2* xy(void* base) const { return (double2*)((char*)base + pack_off); }
-};
 // The preparation launch (the packed panel and every slot's batch means, subg_fused_core's
 // arithmetic) and the replicate launch over `items` replicates of the nseg >= 1 segments in `tab`
 // (device).  c: any segment's constants (n, nd, sqrt_n, l1, l2, crit, mix are call-wide).  Item i of
@@ -528,39 +419,6 @@ struct SubgPairSegConst : SubgSegConst {
   int32_t col_x, col_y;
 };
 static_assert(sizeof(SubgPairSegConst) == 176, "the sub-G table's device table stride");
-// Sub-G table scratch: the segment table | the slot table | the p NI clips lambda_n(n, eta[c]) |
-// the batch means, per column a row of every slot's k means (doubles, [p][nmeans] at pitch mpitch =
-// nmeans rounded up to 2, so each row starts 16-B aligned; a slot's means start at its off) | the p
-// columns as plain doubles, each zero-padded to npad = n rounded up to 4, so every column starts
-// 32-B aligned.  Every region starts 256-B aligned when the base is.  ok is false when a region's
-// bytes (or the total) are not representable.
-struct SubgTableLayout {
-  int64_t npad, mpitch;
-  size_t tab_off = 0, slot_off = 0, clip_off = 0, means_off = 0, cols_off = 0, bytes = 0;
-  bool ok = false;
-  SubgTableLayout(int64_t nseg, int64_t nslots, int64_t nmeans, int64_t n, int64_t p)
-      : npad((n + 3) & ~(int64_t)3), mpitch((nmeans + 1) & ~(int64_t)1) {
-    const size_t lim = SIZE_MAX / 2;
-    if (n < 1 || p < 1 || nseg < 0 || nslots < 0 || nmeans < 0 || (size_t)p > lim / 16 ||
-        (size_t)nseg > lim / (2 * sizeof(SubgPairSegConst)) || (size_t)nslots > lim / (4 * sizeof(SubgMeanSlot)) ||
-        (size_t)nmeans > lim / 16)
-      return;
-    slot_off = al256((size_t)nseg * sizeof(SubgPairSegConst));
-    clip_off = slot_off + al256((size_t)nslots * sizeof(SubgMeanSlot));
-    means_off = clip_off + al256((size_t)p * sizeof(double));
-    const size_t row_bytes = (size_t)mpitch * sizeof(double), col_bytes = (size_t)npad * sizeof(double);
-    if (means_off > lim || (row_bytes && (size_t)p > (lim - means_off) / row_bytes)) return;
-    cols_off = means_off + al256((size_t)p * row_bytes);
-    if (cols_off > lim || (size_t)p > (lim - cols_off) / col_bytes) return;
-    bytes = cols_off + (size_t)p * col_bytes;
-    ok = true;
-  }
-  SubgPairSegConst* tab(void* base) const { return (SubgPairSegConst*)((char*)base + tab_off); }
-  SubgMeanSlot* slots(void* base) const { return (SubgMeanSlot*)((char*)base + slot_off); }
-  double* clips(void* base) const { return (double*)((char*)base + clip_off); }
-  double* means(void* base) const { return (double*)((char*)base + means_off); }
-  double* cols(void* base) const { return (double*)((char*)base + cols_off); }
-};
 // The preparation launch (every column of D copied to pitch npad, and every (column, slot)'s batch
 // means of the column clipped at clips[c]: k_subg_panel_prep's arithmetic, one writer per value) and
 // the replicate launch over `items` replicates of the nseg >= 1 segments in `tab` (device), as
@@ -580,20 +438,6 @@ struct SignSegConst {
   int64_t first;     // the segment's first work item: the sum of the reps before it
   int64_t out_row;
 };
-// Sign-panel scratch: head (the four clipped means, 256 B) | the segment table | the packed panel
-// (xc, yc) of n rounded up to a whole 4-sample flip block.  Every region starts 256-B aligned when
-// the base is.
-struct SignPanelLayout {
-  int64_t npad;
-  size_t tab_off, pack_off, bytes;
-  SignPanelLayout(int64_t nseg, int64_t n)
-      : npad((n + 3) & ~(int64_t)3), tab_off(256),
-        pack_off(tab_off + al256((size_t)nseg * sizeof(SignSegConst))),
-        bytes(pack_off + (size_t)npad * 2 * sizeof(double)) {}
-  double* means(void* base) const { return (double*)base; }
-  SignSegConst* tab(void* base) const { return (SignSegConst*)((char*)base + tab_off); }
-  void* xyc(void* base) const { return (char*)base + pack_off; }
-};
 // The preparation launch (clip, the four double-double sums and their means, the packed panel) and
 // the replicate launch over `items` replicates of the nseg >= 1 segments in `tab` (device).  c: any
 // segment's constants (n, normalise, L, nd are call-wide).  Item i of segment s is replicate
@@ -606,30 +450,6 @@ int launch_sign_panel(const SignConst& c, const double* X, const double* Y, doub
 // A sign-panel segment and the two columns it reads: X = column col_x, Y = column col_y.
 struct SignPairSegConst : SignSegConst {
   int32_t col_x, col_y;
-};
-// Sign-table scratch: the per-column means (mean(xc), mean(xc^2) of column c at means[2 c],
-// means[2 c + 1]) | the segment table | the p clipped columns as plain doubles, each zero-padded
-// to npad = n rounded up to a whole 4-sample flip block, so every column starts 32-B aligned.
-// Every region starts 256-B aligned when the base is.  ok is false when p * npad * 8 bytes (or the
-// total) is not representable.
-struct SignTableLayout {
-  int64_t npad;
-  size_t tab_off = 0, cols_off = 0, bytes = 0;
-  bool ok = false;
-  SignTableLayout(int64_t nseg, int64_t n, int64_t p) : npad((n + 3) & ~(int64_t)3) {
-    const size_t lim = SIZE_MAX / 2;
-    if (n < 1 || p < 1 || nseg < 0 || (size_t)p > lim / 16 || (size_t)nseg > lim / sizeof(SignPairSegConst))
-      return;
-    tab_off = al256((size_t)p * 2 * sizeof(double));
-    cols_off = tab_off + al256((size_t)nseg * sizeof(SignPairSegConst));
-    const size_t col_bytes = (size_t)npad * sizeof(double);
-    if ((size_t)p > (lim - cols_off) / col_bytes) return;
-    bytes = cols_off + (size_t)p * col_bytes;
-    ok = true;
-  }
-  double* means(void* base) const { return (double*)base; }
-  SignPairSegConst* tab(void* base) const { return (SignPairSegConst*)((char*)base + tab_off); }
-  double* cols(void* base) const { return (double*)((char*)base + cols_off); }
 };
 // The preparation launch (one workgroup per column of D: clip, the two double-double sums and
 // their means in k_sign_panel_prep's order, the column stored at pitch npad) and the replicate
@@ -675,23 +495,6 @@ struct HrsNoise {
   double *lap_x, *lap_y, *lap_local, *lap_central, *mix_z, *mix_l;
 };
 int launch_hrs_noise(const HrsNoise& j, int64_t reps, void* stream);
-// The seven arrays of cr replicates in one buffer: perm [cr][k m] i32 | lap_x, lap_y [cr][k] |
-// lap_local [cr][n] | lap_central [cr] | mix_z, mix_l [cr][nsim].  cr = 1 gives the bytes per
-// replicate a buffer is sized by; a chunk's layout fits cr times that.
-struct HrsNoiseLayout {
-  size_t off[7], bytes = 0;
-  HrsNoiseLayout(int64_t n, int64_t k, int64_t m, int64_t nsim, int64_t cr) {
-    const size_t b[7] = {(size_t)cr * k * m * 4, (size_t)cr * k * 8, (size_t)cr * k * 8,
-                         (size_t)cr * n * 8,     (size_t)cr * 8,     (size_t)cr * nsim * 8,
-                         (size_t)cr * nsim * 8};
-    for (int i = 0; i < 7; ++i) { off[i] = bytes; bytes += al256(b[i]); }
-  }
-  void point(char* base, HrsNoise& j) const {   // j's seven pointers over `base`
-    j.perm = (int32_t*)(base + off[0]);
-    double** const d[6] = {&j.lap_x, &j.lap_y, &j.lap_local, &j.lap_central, &j.mix_z, &j.mix_l};
-    for (int i = 0; i < 6; ++i) *d[i] = (double*)(base + off[i + 1]);
-  }
-};
 int launch_dp_sd(const double* x, int64_t n, double lo, double hi, double s_mu, double s_m2,
                  const double* lap2, double* out2, void* stream);
 // R-surface transforms (dcor_premat.hip): the arithmetic half of the R wrappers' DGPs and DP

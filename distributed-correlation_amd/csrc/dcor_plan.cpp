@@ -219,48 +219,43 @@ int64_t hrs_chunk(size_t per, int64_t reps, size_t budget, int64_t cap) {
 // ------------------------------------------------------------------ segment planners
 namespace {
 
-// What the four segment types differ in: the name(s) of eps, and the table's columns.
-template <class Seg> bool eps_ok(const Seg& g) { return g.eps1 > 0.0 && g.eps2 > 0.0; }
-bool eps_ok(const dcor_hrs_segment& g) { return g.eps > 0.0; }
-bool eps_ok(const dcor_hrs_pair_segment& g) { return g.eps > 0.0; }
-bool eps_ok(const dcor_subg_segment& g) {
-  return g.eps1 > 0.0 && g.eps2 > 0.0 && std::isfinite(g.eps1) && std::isfinite(g.eps2);
-}
-template <class Seg> const char* eps_names(const Seg&) { return "eps1, eps2"; }
-const char* eps_names(const dcor_hrs_segment&) { return "eps"; }
-const char* eps_names(const dcor_hrs_pair_segment&) { return "eps"; }
-bool eps_ok(const dcor_subg_pair_segment& g) {
-  return g.eps1 > 0.0 && g.eps2 > 0.0 && std::isfinite(g.eps1) && std::isfinite(g.eps2);
-}
-const char* eps_names(const dcor_subg_segment&) { return "finite eps1, eps2"; }
-const char* eps_names(const dcor_subg_pair_segment&) { return "finite eps1, eps2"; }
-template <class Seg> int check_columns(const char*, const Seg&, int64_t, int64_t) { return DCOR_OK; }
-template <class Seg> int columns_in_range(const char* entry, const Seg& g, int64_t i, int64_t p) {
-  if (g.col_x < 0 || g.col_x >= p || g.col_y < 0 || g.col_y >= p)
-    return fail(DCOR_EINVAL, "%s: segment %lld: columns (%d, %d) outside [0, %lld)", entry, (long long)i,
-                (int)g.col_x, (int)g.col_y, (long long)p);
-  return DCOR_OK;
-}
-int check_columns(const char* entry, const dcor_sign_pair_segment& g, int64_t i, int64_t p) {
-  return columns_in_range(entry, g, i, p);
-}
-int check_columns(const char* entry, const dcor_hrs_pair_segment& g, int64_t i, int64_t p) {
-  return columns_in_range(entry, g, i, p);
-}
-int check_columns(const char* entry, const dcor_subg_pair_segment& g, int64_t i, int64_t p) {
-  return columns_in_range(entry, g, i, p);
-}
-void set_columns(SignSegConst&, const dcor_sign_segment&) {}
-void set_columns(SignPairSegConst& t, const dcor_sign_pair_segment& g) { t.col_x = g.col_x; t.col_y = g.col_y; }
+// What the segment types differ in, one trait each: the test of its eps field(s), their wording in
+// the message, and whether the segment names two columns of a table.
+struct OneEps {
+  template <class Seg> static bool eps_ok(const Seg& g) { return g.eps > 0.0; }
+  static constexpr const char* eps_names = "eps";
+};
+struct TwoEps {
+  template <class Seg> static bool eps_ok(const Seg& g) { return g.eps1 > 0.0 && g.eps2 > 0.0; }
+  static constexpr const char* eps_names = "eps1, eps2";
+};
+struct TwoFiniteEps {
+  template <class Seg> static bool eps_ok(const Seg& g) {
+    return TwoEps::eps_ok(g) && std::isfinite(g.eps1) && std::isfinite(g.eps2);
+  }
+  static constexpr const char* eps_names = "finite eps1, eps2";
+};
+template <class Seg> struct SegTrait;
+template <> struct SegTrait<dcor_hrs_segment> : OneEps { static constexpr bool columns = false; };
+template <> struct SegTrait<dcor_hrs_pair_segment> : OneEps { static constexpr bool columns = true; };
+template <> struct SegTrait<dcor_sign_segment> : TwoEps { static constexpr bool columns = false; };
+template <> struct SegTrait<dcor_sign_pair_segment> : TwoEps { static constexpr bool columns = true; };
+template <> struct SegTrait<dcor_subg_segment> : TwoFiniteEps { static constexpr bool columns = false; };
+template <> struct SegTrait<dcor_subg_pair_segment> : TwoFiniteEps { static constexpr bool columns = true; };
 
 // Segment i's own fields (they need nothing but the segment; p: the table's column count), its
 // replicates added to `items`; cap: at most 2^31 - 1 replicates in one call.
 template <class Seg>
 int segment_head(const char* entry, const Seg& g, int64_t i, int64_t p, bool cap, int64_t& items) {
-  if (g.reps < 0 || g.rep_begin < 0 || g.out_row < 0 || !eps_ok(g))
+  using Tr = SegTrait<Seg>;
+  if (g.reps < 0 || g.rep_begin < 0 || g.out_row < 0 || !Tr::eps_ok(g))
     return fail(DCOR_EINVAL, "%s: segment %lld: need %s > 0, reps, rep_begin, out_row >= 0", entry,
-                (long long)i, eps_names(g));
-  if (int st = check_columns(entry, g, i, p)) return st;
+                (long long)i, Tr::eps_names);
+  if constexpr (Tr::columns) {
+    if (g.col_x < 0 || g.col_x >= p || g.col_y < 0 || g.col_y >= p)
+      return fail(DCOR_EINVAL, "%s: segment %lld: columns (%d, %d) outside [0, %lld)", entry, (long long)i,
+                  (int)g.col_x, (int)g.col_y, (long long)p);
+  }
   if (rep_range_exceeds(g.rep_begin, g.reps))
     return fail(DCOR_EINVAL, "%s: segment %lld: replicate range exceeds 2^32", entry, (long long)i);
   items += g.reps;   // reps <= 2^32 each: no overflow below 2^31 segments
@@ -292,7 +287,7 @@ int sign_segment_table(const Desc& d, const Seg* segs, int64_t nseg, std::vector
     t.s.k0 = (uint32_t)g.seed; t.s.k1 = (uint32_t)(g.seed >> 32);
     t.s.rep_begin = g.rep_begin;
     t.first = first; t.out_row = g.out_row;
-    set_columns(t, g);
+    if constexpr (SegTrait<Seg>::columns) { t.col_x = g.col_x; t.col_y = g.col_y; }
     first += g.reps;
     tab.push_back(t);
   }
@@ -350,11 +345,13 @@ void subg_segment_record(const SubgConst& a, const Seg& g, int64_t first, std::v
   t.mean_off = slots[d].off;
   t.first = first; t.out_row = g.out_row;
 }
+int64_t mean_count(const std::vector<SubgMeanSlot>& slots) {   // the batch means of a call
+  return slots.empty() ? 0 : slots.back().off + slots.back().k;
+}
 
-// The checks the two HRS table entries share (T: dcor_hrs_table_desc or dcor_hrs_table_na_desc), in
-// the entries' order: p and ld; D's alignment and every lam[c]; alpha and nsim, as every segment's
-// make_subg would refuse them.
-template <class T> int hrs_table_shape(const char* entry, const T& t) {
+// The checks table entries share, in the entries' order: p and ld (every table descriptor); D's
+// alignment and every lam[c] (T: dcor_hrs_table_desc or dcor_hrs_table_na_desc).
+template <class T> int table_shape(const char* entry, const T& t) {
   if (t.p < 1 || t.p > 0x7fffffffLL)
     return fail(DCOR_EINVAL, "%s: p must be in [1, 2^31) (got %lld)", entry, (long long)t.p);
   if (t.ld < t.n)
@@ -369,10 +366,11 @@ template <class T> int hrs_table_clips(const char* entry, const T& t) {
                   t.lam[c]);
   return DCOR_OK;
 }
-template <class T> int hrs_table_mix(const T& t) {
+// alpha and nsim of a sub-G or HRS call, as every segment's make_subg would refuse them
+int check_alpha_nsim(int64_t n, double alpha, int64_t nsim) {
   MixConst mx;
-  if (int st = check_common(t.n, 1.0, 1.0, t.alpha)) return st;
-  return make_mix(t.nsim, t.alpha, mx);
+  if (int st = check_common(n, 1.0, 1.0, alpha)) return st;
+  return make_mix(nsim, alpha, mx);
 }
 
 }  // namespace
@@ -446,23 +444,24 @@ int plan_hrs_fused_sweep(const dcor_premat_subg* base, const dcor_panel* panel,
 }
 
 int plan_sign_panel(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs, int64_t nseg,
-                    std::vector<SignSegConst>& tab, int64_t* items) {
+                    SignPanelPlan& plan) {
+  plan = SignPanelPlan();
   if (!p->X || !p->Y) return fail(DCOR_EINVAL, "sign_panel: null argument (X, Y)");
-  if (int st = segment_heads("sign_panel", segs, nseg, 0, items)) return st;
-  return sign_segment_table(*p, segs, nseg, tab);
+  if (int st = segment_heads("sign_panel", segs, nseg, 0, &plan.items)) return st;
+  if (int st = sign_segment_table(*p, segs, nseg, plan.tab)) return st;
+  plan.lay = SignPanelLayout((int64_t)plan.tab.size(), p->n);
+  return DCOR_OK;
 }
 
 int plan_sign_table(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs, int64_t nseg,
-                    std::vector<SignPairSegConst>& tab, int64_t* items) {
+                    SignTablePlan& plan) {
+  plan = SignTablePlan();
   if (!t->D) return fail(DCOR_EINVAL, "sign_table: null argument (D)");
-  if (t->p < 1 || t->p > 0x7fffffffLL)
-    return fail(DCOR_EINVAL, "sign_table: p must be in [1, 2^31) (got %lld)", (long long)t->p);
-  if (t->ld < t->n)
-    return fail(DCOR_EINVAL, "sign_table: ld = %lld < n = %lld", (long long)t->ld, (long long)t->n);
-  if (int st = segment_heads("sign_table", segs, nseg, t->p, items)) return st;
-  if (int st = sign_segment_table(*t, segs, nseg, tab)) return st;
-  // after make_sign: n is in [1, 2^31) here
-  if (!SignTableLayout((int64_t)tab.size(), t->n, t->p).ok)
+  if (int st = table_shape("sign_table", *t)) return st;
+  if (int st = segment_heads("sign_table", segs, nseg, t->p, &plan.items)) return st;
+  if (int st = sign_segment_table(*t, segs, nseg, plan.tab)) return st;
+  plan.lay = SignTableLayout((int64_t)plan.tab.size(), t->n, t->p);
+  if (!plan.lay.ok)
     return fail(DCOR_EINVAL, "sign_table: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)",
                 (long long)t->p, (long long)t->n);
   return DCOR_OK;
@@ -486,21 +485,21 @@ dcor_premat_subg hrs_pair_desc(const dcor_hrs_table_desc& t, const dcor_hrs_pair
 }
 
 int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs, int64_t nseg,
-                   std::vector<HrsPairSegConst>& tab, int64_t* items, int64_t* max_km) {
-  *items = 0; *max_km = 0;
+                   HrsTablePlan& plan) {
+  plan = HrsTablePlan();
   if (!t->D || !t->lam) return fail(DCOR_EINVAL, "hrs_table: null argument (D, lam)");
   if (t->n < 2 || t->n > DCOR_DICT_NMAX)
     return fail(DCOR_EINVAL, "hrs_table: n must be in [2, %d] (got %lld): the kernel keeps a replicate's "
                 "u16 batch indices in LDS and there is no fallback for a larger table", DCOR_DICT_NMAX,
                 (long long)t->n);
-  if (int st = hrs_table_shape("hrs_table", *t)) return st;
-  if (!HrsTableLayout(0, 0, t->n, t->p).ok)
+  if (int st = table_shape("hrs_table", *t)) return st;
+  if (!HrsTableLayout::columns(t->n, t->p).ok)
     return fail(DCOR_EINVAL, "hrs_table: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)",
                 (long long)t->p, (long long)t->n);
   if (int st = hrs_table_clips("hrs_table", *t)) return st;
   if (!(t->delta > 0.0)) return fail(DCOR_EINVAL, "hrs_table: delta must be positive");
-  if (int st = hrs_table_mix(*t)) return st;
-  if (int st = segment_heads("hrs_table", segs, nseg, t->p, items)) return st;
+  if (int st = check_alpha_nsim(t->n, t->alpha, t->nsim)) return st;
+  if (int st = segment_heads("hrs_table", segs, nseg, t->p, &plan.items)) return st;
   // every segment's launch constants: those of the reference call on its pair, lam and eps
   int64_t first = 0;
   for (int64_t i = 0; i < nseg; ++i) {
@@ -509,15 +508,17 @@ int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* se
     PrematSubgConst pc;
     if (int st = premat_subg_const(&q, pc)) return st;
     if (g.reps == 0) continue;
+    if (plan.tab.empty()) { plan.c0 = pc; plan.c0.X = plan.c0.Y = nullptr; }
     HrsPairSegConst r;
     std::memset(&r, 0, sizeof(r));
     hrs_segment_record(pc, g, first, r);
     r.col_x = g.col_x; r.col_y = g.col_y;
     first += g.reps;
-    tab.push_back(r);
-    *max_km = std::max(*max_km, pc.s.k * (int64_t)pc.s.m);
+    plan.tab.push_back(r);
+    plan.max_km = std::max(plan.max_km, pc.s.k * (int64_t)pc.s.m);
   }
-  if (!HrsTableLayout(*items, (int64_t)tab.size(), t->n, t->p).ok)
+  plan.lay = HrsTableLayout(plan.items, (int64_t)plan.tab.size(), t->n, t->p);
+  if (!plan.lay.ok)
     return fail(DCOR_EINVAL, "hrs_table: scratch bytes overflow (p = %lld, n = %lld)", (long long)t->p,
                 (long long)t->n);
   return DCOR_OK;
@@ -534,23 +535,22 @@ int64_t hrs_pair_count(const uint64_t* valid, int64_t n, int64_t col_x, int64_t 
 }
 
 int plan_hrs_table_pairwise(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair_segment* segs,
-                            int64_t nseg, std::vector<HrsPairNaSegConst>& tab,
-                            std::vector<HrsPairSlot>& slots, PrematSubgConst* c0, int64_t* panel_elems,
-                            int64_t* items, int64_t* max_km) {
+                            int64_t nseg, HrsPairTablePlan& plan) {
   const char* const entry = "hrs_table_pairwise";
-  *items = 0; *max_km = 0; *panel_elems = 0;
+  plan = HrsPairTablePlan();
+  auto &tab = plan.tab; auto &slots = plan.slots;
   if (!t->D || !t->lam || !t->valid) return fail(DCOR_EINVAL, "%s: null argument (D, lam, valid)", entry);
   if (t->n < 2 || t->n > 0x7fffffffLL)
     return fail(DCOR_EINVAL, "%s: n must be in [2, 2^31) (got %lld)", entry, (long long)t->n);
-  if (int st = hrs_table_shape(entry, *t)) return st;
-  if (!HrsPairTableLayout(0, 0, 0, t->n, t->p, 0).ok)
+  if (int st = table_shape(entry, *t)) return st;
+  if (!HrsPairTableLayout::columns(t->n, t->p).ok)
     return fail(DCOR_EINVAL, "%s: p * ceil(n / 64) * 8 scratch bytes overflow (p = %lld, n = %lld)", entry,
                 (long long)t->p, (long long)t->n);
   if (int st = hrs_table_clips(entry, *t)) return st;
   if (!(t->delta > 0.0) && !std::isnan(t->delta))
     return fail(DCOR_EINVAL, "%s: delta must be positive, or NaN for 1 / n_ab per pair", entry);
-  if (int st = hrs_table_mix(*t)) return st;
-  if (int st = segment_heads(entry, segs, nseg, t->p, items)) return st;
+  if (int st = check_alpha_nsim(t->n, t->alpha, t->nsim)) return st;
+  if (int st = segment_heads(entry, segs, nseg, t->p, &plan.items)) return st;
   // every segment's pair, then its launch constants: those of the reference call on the pair's
   // n_ab compacted rows, lam and eps
   struct Pair { int64_t n_ab, slot; };   // slot: -1 until a segment with replicates names the pair
@@ -573,13 +573,13 @@ int plan_hrs_table_pairwise(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair
     PrematSubgConst pc;
     if (int st = premat_subg_const(&q, pc)) return st;
     if (g.reps == 0) continue;
-    if (tab.empty()) *c0 = pc;
+    if (tab.empty()) { plan.c0 = pc; plan.c0.X = plan.c0.Y = nullptr; }
     if (pr.slot < 0) {   // a pair not run before: its panel follows the others'
       HrsPairSlot sl;
       std::memset(&sl, 0, sizeof(sl));
-      sl.n_ab = pr.n_ab; sl.panel = *panel_elems;
+      sl.n_ab = pr.n_ab; sl.panel = plan.panel_elems;
       sl.col_x = g.col_x; sl.col_y = g.col_y;
-      *panel_elems += hrs_pair_panel_elems(pr.n_ab);
+      plan.panel_elems += hrs_pair_panel_elems(pr.n_ab);
       pr.slot = (int64_t)slots.size();
       slots.push_back(sl);
     }
@@ -592,18 +592,19 @@ int plan_hrs_table_pairwise(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair
     r.panel = slots[(size_t)pr.slot].panel;
     first += g.reps;
     tab.push_back(r);
-    *max_km = std::max(*max_km, pc.s.k * (int64_t)pc.s.m);
+    plan.max_km = std::max(plan.max_km, pc.s.k * (int64_t)pc.s.m);
   }
-  if (!HrsPairTableLayout(*items, (int64_t)tab.size(), (int64_t)slots.size(), t->n, t->p, *panel_elems).ok)
+  plan.lay = HrsPairTableLayout(plan.items, (int64_t)tab.size(), (int64_t)slots.size(), t->n, t->p, plan.panel_elems);
+  if (!plan.lay.ok)
     return fail(DCOR_EINVAL, "%s: scratch bytes overflow (p = %lld, n = %lld)", entry, (long long)t->p,
                 (long long)t->n);
   return DCOR_OK;
 }
 
 int plan_subg_panel(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs, int64_t nseg,
-                    std::vector<SubgSegConst>& tab, std::vector<SubgMeanSlot>& slots, SubgConst* c0,
-                    int64_t* items) {
-  *items = 0;
+                    SubgPanelPlan& plan) {
+  plan = SubgPanelPlan();
+  auto &tab = plan.tab; auto &slots = plan.slots;
   if (!p->X || !p->Y) return fail(DCOR_EINVAL, "subg_panel: null argument (X, Y)");
   if (((uintptr_t)p->X | (uintptr_t)p->Y) & 7)
     return fail(DCOR_EINVAL, "subg_panel: X and Y must be aligned to 8 bytes");
@@ -611,12 +612,8 @@ int plan_subg_panel(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs
     return fail(DCOR_EINVAL, "subg_panel: n must be in [1, 2^31) (got %lld)", (long long)p->n);
   if (!(p->eta1 > 0.0) || !(p->eta2 > 0.0) || !std::isfinite(p->eta1) || !std::isfinite(p->eta2))
     return fail(DCOR_EINVAL, "subg_panel: eta1, eta2 must be finite and > 0 (got %g, %g)", p->eta1, p->eta2);
-  {  // alpha and nsim, as every segment's make_subg would refuse them
-    MixConst mx;
-    if (int st = check_common(p->n, 1.0, 1.0, p->alpha)) return st;
-    if (int st = make_mix(p->nsim, p->alpha, mx)) return st;
-  }
-  if (int st = segment_heads("subg_panel", segs, nseg, 0, items)) return st;
+  if (int st = check_alpha_nsim(p->n, p->alpha, p->nsim)) return st;
+  if (int st = segment_heads("subg_panel", segs, nseg, 0, &plan.items)) return st;
   // every segment's launch constants: make_subg's own, the simulation variant (hrs = 0, no override)
   int64_t first = 0;
   for (int64_t i = 0; i < nseg; ++i) {
@@ -626,40 +623,34 @@ int plan_subg_panel(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs
                            NAN, p->nsim, a, nullptr, nullptr))
       return st;
     if (g.reps == 0) continue;
-    if (tab.empty()) *c0 = a;
+    if (tab.empty()) plan.c0 = a;
     SubgSegConst t;
     subg_segment_record(a, g, first, slots, t);
     first += g.reps;
     tab.push_back(t);
   }
+  plan.lay = SubgPanelLayout((int64_t)tab.size(), (int64_t)slots.size(), mean_count(slots), p->n);
   return DCOR_OK;
 }
 
 int plan_subg_table(const dcor_subg_table_desc* t, const dcor_subg_pair_segment* segs, int64_t nseg,
-                    std::vector<SubgPairSegConst>& tab, std::vector<SubgMeanSlot>& slots,
-                    std::vector<double>& clips, SubgConst* c0, int64_t* items) {
-  *items = 0;
+                    SubgTablePlan& plan) {
+  plan = SubgTablePlan();
+  auto &tab = plan.tab; auto &slots = plan.slots;
   if (!t->D || !t->eta) return fail(DCOR_EINVAL, "subg_table: null argument (D, eta)");
   if ((uintptr_t)t->D & 7) return fail(DCOR_EINVAL, "subg_table: D must be aligned to 8 bytes");
   if (t->n < 1 || t->n > 0x7fffffffLL)
     return fail(DCOR_EINVAL, "subg_table: n must be in [1, 2^31) (got %lld)", (long long)t->n);
-  if (t->p < 1 || t->p > 0x7fffffffLL)
-    return fail(DCOR_EINVAL, "subg_table: p must be in [1, 2^31) (got %lld)", (long long)t->p);
-  if (t->ld < t->n)
-    return fail(DCOR_EINVAL, "subg_table: ld = %lld < n = %lld", (long long)t->ld, (long long)t->n);
-  if (!SubgTableLayout(0, 0, 0, t->n, t->p).ok)
+  if (int st = table_shape("subg_table", *t)) return st;
+  if (!SubgTableLayout::columns(t->n, t->p).ok)
     return fail(DCOR_EINVAL, "subg_table: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)",
                 (long long)t->p, (long long)t->n);
   for (int64_t c = 0; c < t->p; ++c)
     if (!std::isfinite(t->eta[c]) || !(t->eta[c] > 0.0))
       return fail(DCOR_EINVAL, "subg_table: column %lld: eta must be finite and > 0 (got %g)", (long long)c,
                   t->eta[c]);
-  {  // alpha and nsim, as every segment's make_subg would refuse them
-    MixConst mx;
-    if (int st = check_common(t->n, 1.0, 1.0, t->alpha)) return st;
-    if (int st = make_mix(t->nsim, t->alpha, mx)) return st;
-  }
-  if (int st = segment_heads("subg_table", segs, nseg, t->p, items)) return st;
+  if (int st = check_alpha_nsim(t->n, t->alpha, t->nsim)) return st;
+  if (int st = segment_heads("subg_table", segs, nseg, t->p, &plan.items)) return st;
   // every segment's launch constants: those of the reference call on its pair, eta and eps
   int64_t first = 0;
   for (int64_t i = 0; i < nseg; ++i) {
@@ -670,8 +661,9 @@ int plan_subg_table(const dcor_subg_table_desc* t, const dcor_subg_pair_segment*
       return st;
     if (g.reps == 0) continue;
     if (tab.empty()) {   // the call-wide constants alone: nothing of eta, eps or the key
-      std::memset(c0, 0, sizeof(*c0));
-      c0->n = a.n; c0->nd = a.nd; c0->sqrt_n = a.sqrt_n; c0->crit = a.crit; c0->mix = a.mix;
+      SubgConst& c0 = plan.c0;
+      std::memset(&c0, 0, sizeof(c0));
+      c0.n = a.n; c0.nd = a.nd; c0.sqrt_n = a.sqrt_n; c0.crit = a.crit; c0.mix = a.mix;
     }
     SubgPairSegConst r;
     std::memset(&r, 0, sizeof(r));
@@ -680,13 +672,14 @@ int plan_subg_table(const dcor_subg_table_desc* t, const dcor_subg_pair_segment*
     first += g.reps;
     tab.push_back(r);
   }
-  const int64_t nmeans = slots.empty() ? 0 : slots.back().off + slots.back().k;
-  if (!SubgTableLayout((int64_t)tab.size(), (int64_t)slots.size(), nmeans, t->n, t->p).ok)
+  const int64_t nmeans = mean_count(slots);
+  plan.lay = SubgTableLayout((int64_t)tab.size(), (int64_t)slots.size(), nmeans, t->n, t->p);
+  if (!plan.lay.ok)
     return fail(DCOR_EINVAL, "subg_table: scratch bytes overflow (p = %lld, n = %lld, %lld batch means per column)",
                 (long long)t->p, (long long)t->n, (long long)nmeans);
   if (!tab.empty()) {   // make_subg's own expression for l1 / l2, so the reference call's clips are these bits
-    clips.resize((size_t)t->p);
-    for (int64_t c = 0; c < t->p; ++c) clips[(size_t)c] = dcor_lambda_n((double)t->n, t->eta[c]);
+    plan.clips.resize((size_t)t->p);
+    for (int64_t c = 0; c < t->p; ++c) plan.clips[(size_t)c] = dcor_lambda_n((double)t->n, t->eta[c]);
   }
   return DCOR_OK;
 }

@@ -1,8 +1,9 @@
 // dcor_plan.h -- the host decisions that need no device: the error reporter, the argument checks,
-// every launch constant (R operation order, cited) and the segment planners of the eight
-// segment-list entries.  Plain C++: neither this header nor dcor_plan.cpp includes the HIP
-// runtime, so the unit compiles, runs and is sanitized with a host compiler alone
-// (tests/host/plan_check.cpp).  Not part of the ABI.
+// every launch constant (R operation order, cited), the scratch layouts (dcor_layout.h) and the
+// segment planners of the eight segment-list entries, one plan struct each.  Plain C++: neither
+// this header nor dcor_plan.cpp includes the HIP runtime, so the unit compiles, runs and is
+// sanitized with a host compiler alone (tests/host/*.cpp over tests/host/check.h).  Not part of
+// the ABI.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -21,6 +22,7 @@ struct alignas(16) double2 { double x, y; };
 
 #include "../../include/dcor.h"
 #include "dcor_engine.h"
+#include "dcor_layout.h"
 
 static_assert(sizeof(double2) == 16 && alignof(double2) == 16, "the scratch layouts' pack stride");
 
@@ -36,7 +38,7 @@ struct dcor_panel {
   int coded;          // host copy of the device flag (read once at create)
   uint16_t* codes() const { return lay.codes(buf); }
   double* dict() const { return lay.dict(buf); }
-  int* ok() const { return lay.ok(buf); }
+  int* ok() const { return lay.ok_flag(buf); }
 };
 
 namespace dcor {
@@ -104,72 +106,80 @@ struct HrsFusedSweepPlan {
 int plan_hrs_fused_sweep(const dcor_premat_subg* base, const dcor_panel* panel,
                          const dcor_hrs_segment* segs, int64_t nseg, HrsFusedSweepPlan& plan);
 
+// ---- the six table entries: int plan_X(desc, segs, nseg, XPlan&).  A planner resets its plan and
+// makes every check of its entry after the null checks of the descriptor, segs and d_out, in the
+// order include/dcor.h documents; a segment without replicates is checked too.  On DCOR_OK the plan
+// is all the entry needs: tab, the records of the segments with reps > 0 in call order; items, the
+// call's replicates; c0, the call-wide constants; lay, the call's scratch, built once. ----
+template <class Record, class Layout> struct TablePlan {
+  std::vector<Record> tab;
+  int64_t items = 0;
+  Layout lay;
+};
+
+// dcor_sign_panel_launch, dcor_sign_table_launch: a record is make_sign's constants with the
+// segment's key, first replicate and place (and columns); the call-wide ones are tab[0].s's.
+using SignPanelPlan = TablePlan<SignSegConst, SignPanelLayout>;
+using SignTablePlan = TablePlan<SignPairSegConst, SignTableLayout>;
 int plan_sign_panel(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs, int64_t nseg,
-                    std::vector<SignSegConst>& tab, int64_t* items);
+                    SignPanelPlan& plan);
 
 // dcor_hrs_table_launch.  The reference call of a segment (include/dcor.h): the descriptor
-// dcor_hrs_fused_launch takes for the pair's columns, clip bounds and eps (lam_x = lam_s =
-// lam[col_x], lam_y = lam_o = lam[col_y], eta = 1, lam_r = lambda_receiver_from_noise; X, Y the
-// columns' addresses, never read here).  g's columns must be in [0, t.p).
+// dcor_hrs_fused_launch takes for the pair's columns, clip bounds and eps (lam_x = lam_s = lam[col_x],
+// lam_y = lam_o = lam[col_y], eta = 1, lam_r = lambda_receiver_from_noise; X, Y the columns'
+// addresses, never read here).  g's columns must be in [0, t.p).
 dcor_premat_subg hrs_pair_desc(const dcor_hrs_table_desc& t, const dcor_hrs_pair_segment& g);
-// Every check of the entry after its null checks of t, segs and d_out, in the header's order (D and
-// lam, n, p, ld, the columns' scratch, every lam[c], delta, alpha, nsim, then the segments' fields,
-// columns and ranges, the replicate cap, every segment's constants), then the table: a kept
-// segment's record holds, field for field, what plan_hrs_fused_sweep builds for hrs_pair_desc.
-// items: the call's replicates; max_km: the largest k m of the kept segments.
+// A record holds, field for field, what plan_hrs_fused_sweep builds for hrs_pair_desc.  c0: the
+// first kept segment's constants with X and Y null; max_km: the largest k m of the kept segments.
+struct HrsTablePlan : TablePlan<HrsPairSegConst, HrsTableLayout> {
+  PrematSubgConst c0{};
+  int64_t max_km = 0;
+};
 int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs, int64_t nseg,
-                   std::vector<HrsPairSegConst>& tab, int64_t* items, int64_t* max_km);
+                   HrsTablePlan& plan);
 
-// dcor_hrs_table_pairwise_launch.  The count of rows present in both columns: popcount of the ANDed
-// mask words (column c's nw = ceil(n / 64) words at valid + c * nw), the last word's bits at i >= n
-// masked off.
+// dcor_hrs_table_pairwise_launch.  The rows present in both columns: popcount of the ANDed mask words
+// (column c's nw = ceil(n / 64) words at valid + c * nw), the last word's bits at i >= n masked off.
 int64_t hrs_pair_count(const uint64_t* valid, int64_t n, int64_t col_x, int64_t col_y);
-// Every check of the entry after its null checks of t, segs and d_out: plan_hrs_table's in its
-// order with the bound on n replaced by 2 <= n < 2^31, valid non-null beside D and lam, delta > 0 or
-// NaN; then per segment (one without replicates too) 2 <= n_ab <= DCOR_DICT_NMAX (the message names
-// the segment and n_ab) and its constants; then the whole scratch.  slots: the distinct ordered
-// pairs of the segments with replicates in order of first use, each with its n_ab and its panel's
-// first element (hrs_pair_panel_elems apart); panel_elems: the panels' double2 elements in all.
-// A kept segment's record holds, field for field, what plan_hrs_fused_sweep builds for
-// hrs_pair_desc at n = n_ab and delta = t->delta or 1 / n_ab, and n_ab, nd, sqrt_n (make_subg's),
-// the Feistel split of ceil(log2 n_ab) bits and its slot's panel.  c0: the first kept segment's
-// constants (the call-wide crit, mix and hrs are read from it; untouched when nothing is kept);
-// items, max_km: as plan_hrs_table's.
+// slots: the distinct ordered pairs of the kept segments in order of first use, each with its n_ab
+// and its panel's first element (hrs_pair_panel_elems apart); panel_elems: the panels' double2
+// elements in all.  A record is plan_hrs_table's at n = n_ab (2 <= n_ab <= DCOR_DICT_NMAX) and delta =
+// t->delta or 1 / n_ab, with n_ab, nd, sqrt_n (make_subg's), the Feistel split of ceil(log2 n_ab)
+// bits and its slot's panel.
+struct HrsPairTablePlan : TablePlan<HrsPairNaSegConst, HrsPairTableLayout> {
+  std::vector<HrsPairSlot> slots;
+  PrematSubgConst c0{};
+  int64_t max_km = 0, panel_elems = 0;
+};
 int plan_hrs_table_pairwise(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair_segment* segs,
-                            int64_t nseg, std::vector<HrsPairNaSegConst>& tab,
-                            std::vector<HrsPairSlot>& slots, PrematSubgConst* c0, int64_t* panel_elems,
-                            int64_t* items, int64_t* max_km);
+                            int64_t nseg, HrsPairTablePlan& plan);
 
-// dcor_subg_panel_launch.  Every check of the entry after its null checks of p, segs and d_out, in
-// the header's order (X and Y, n, eta1 and eta2, alpha, nsim, then the segments' fields and ranges,
-// the replicate cap, every segment's constants), then the table: a kept segment's record holds,
-// field for field, what make_subg yields for (n, eps1, eps2, eta1, eta2, alpha, hrs = 0, nsim).
-// slots: the distinct batch sizes m of the kept segments in order of first use (a record's m_slot
-// names its entry, mean_off that entry's off); c0: the first kept segment's constants (the
-// call-wide ones are read from it); items: the call's replicates.
+// dcor_subg_panel_launch.  A record holds, field for field, what make_subg yields for (n, eps1, eps2,
+// eta1, eta2, alpha, hrs = 0, nsim).  slots: the distinct batch sizes m of the kept segments in order
+// of first use (m_slot names a record's entry, mean_off that entry's off); c0: the first kept's.
+struct SubgPanelPlan : TablePlan<SubgSegConst, SubgPanelLayout> {
+  std::vector<SubgMeanSlot> slots;
+  SubgConst c0{};
+};
 int plan_subg_panel(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs, int64_t nseg,
-                    std::vector<SubgSegConst>& tab, std::vector<SubgMeanSlot>& slots, SubgConst* c0,
-                    int64_t* items);
+                    SubgPanelPlan& plan);
 
-// dcor_subg_table_launch.  The reference call of a segment (include/dcor.h): dcor_subg_panel_launch
-// on X = column col_x, Y = column col_y with eta1 = eta[col_x], eta2 = eta[col_y].  Every check of
-// the entry after its null checks of t, segs and d_out, in the header's order (D and eta, D's
-// alignment, n, p, ld, the columns' scratch, every eta[c], alpha, nsim, then the segments' fields,
-// columns and ranges, the replicate cap, every segment's constants, the whole scratch), then the
-// table: a kept segment's record holds, field for field, what plan_subg_panel builds for the
-// reference call, and its columns.  slots: as plan_subg_panel's; clips: the p NI clips
-// lambda_n(n, eta[c]) (make_subg's expression for l1 / l2; empty when nothing is kept); c0: n, nd,
-// sqrt_n, crit and mix, everything else zero; items: the call's replicates.
+// dcor_subg_table_launch.  A record is plan_subg_panel's for the segment's reference call (X = column
+// col_x, Y = column col_y, eta1 = eta[col_x], eta2 = eta[col_y]), and its columns.  clips: the p NI
+// clips lambda_n(n, eta[c]) (empty when nothing is kept); c0: n, nd, sqrt_n, crit, mix, else zero.
+struct SubgTablePlan : TablePlan<SubgPairSegConst, SubgTableLayout> {
+  std::vector<SubgMeanSlot> slots;
+  std::vector<double> clips;
+  SubgConst c0{};
+};
 int plan_subg_table(const dcor_subg_table_desc* t, const dcor_subg_pair_segment* segs, int64_t nseg,
-                    std::vector<SubgPairSegConst>& tab, std::vector<SubgMeanSlot>& slots,
-                    std::vector<double>& clips, SubgConst* c0, int64_t* items);
+                    SubgTablePlan& plan);
 
 #pragma GCC visibility pop
 
-// C linkage and exported, as it has been since the table entry was added: the library's dynamic
-// symbols stay what they were.
+// C linkage and exported: the one planner among the library's dynamic symbols.
 extern "C" int plan_sign_table(const dcor_sign_table_desc* t, const dcor_sign_pair_segment* segs,
-                               int64_t nseg, std::vector<SignPairSegConst>& tab, int64_t* items);
+                               int64_t nseg, SignTablePlan& plan);
 
 }  // namespace host
 }  // namespace dcor

@@ -3,51 +3,11 @@
 // counts n_ab against a per-row loop (the compaction-edge masks, the tail of the last word
 // included); the slots (the distinct ordered pairs, their panels 256-B aligned and disjoint); every
 // segment record against the record plan_hrs_fused_sweep builds for a panel of n_ab samples with
-// the pair's delta, as bytes over the fields the two share; every rejection's code and message.  The
-// segment and mask arrays are heap blocks of exactly their length, so a planner that reads past them
-// is caught when the program is built with a sanitizer.  Exit status 0: every check held.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <string>
+// the pair's delta, as bytes over the fields the two share; every rejection's code and message.
+// Harness: check.h.
 #include <utility>
-#include <vector>
 
-#include "dcor_plan.h"
-
-using namespace dcor;
-using namespace dcor::host;
-
-#define CHECK(cond)                                                        \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      std::fprintf(stderr, "%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #cond); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
-
-static std::string last_error() {
-  char buf[512];
-  dcor_last_error(buf, sizeof(buf));
-  return buf;
-}
-#define CHECK_FAILS(call, code, msg)                                       \
-  do {                                                                     \
-    CHECK((call) == (code));                                               \
-    if (last_error().find(msg) == std::string::npos) {                     \
-      std::fprintf(stderr, "%s:%d: message '%s'\n", __FILE__, __LINE__, last_error().c_str()); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
-
-template <class T>
-static std::unique_ptr<T[]> heap(const std::vector<T>& v) {   // exactly v.size() elements
-  std::unique_ptr<T[]> p(new T[v.size() ? v.size() : 1]);
-  for (size_t i = 0; i < v.size(); ++i) p[i] = v[i];
-  return p;
-}
+#include "check.h"
 
 static const double* const kD = (const double*)4096;   // never dereferenced
 static const double kLam[4] = {1.75, 2.5, 3.0625, 0.9};
@@ -180,13 +140,13 @@ static void check_records(int64_t n, double delta) {
   for (const auto& reps : kReps) {
     const std::vector<dcor_hrs_pair_segment> segs = segments(reps);
     const auto hs = heap(segs);
-    std::vector<HrsPairNaSegConst> tab;
-    std::vector<HrsPairSlot> slots;
-    PrematSubgConst c0;
-    std::memset(&c0, 0, sizeof(c0));
-    int64_t items = -1, max_km = -1, panel_elems = -1;
-    CHECK(plan_hrs_table_pairwise(&t, hs.get(), (int64_t)segs.size(), tab, slots, &c0, &panel_elems, &items,
-                                  &max_km) == DCOR_OK);
+    HrsPairTablePlan pl;
+    pl.items = pl.max_km = pl.panel_elems = -1;
+    CHECK(plan_hrs_table_pairwise(&t, hs.get(), (int64_t)segs.size(), pl) == DCOR_OK);
+    const std::vector<HrsPairNaSegConst>& tab = pl.tab;
+    const std::vector<HrsPairSlot>& slots = pl.slots;
+    const PrematSubgConst& c0 = pl.c0;
+    const int64_t items = pl.items, max_km = pl.max_km, panel_elems = pl.panel_elems;
     // the slots: the distinct ordered pairs of the kept segments in order of first use
     std::vector<std::pair<int, int>> want_slots;
     for (size_t i = 0; i < reps.size(); ++i) {
@@ -247,6 +207,8 @@ static void check_records(int64_t n, double delta) {
     }
     CHECK(j == tab.size());
     CHECK(items == first && max_km == want_km);
+    CHECK(pl.lay.ok && pl.lay.bytes == HrsPairTableLayout(items, (int64_t)tab.size(), (int64_t)slots.size(), t.n,
+                                                         t.p, panel_elems).bytes);
   }
 }
 
@@ -261,11 +223,11 @@ static void check_tiny_pairs() {
       dcor_hrs_pair_segment g;
       std::memset(&g, 0, sizeof(g));
       g.eps = 2.0; g.reps = 1; g.col_x = 0; g.col_y = c;
-      std::vector<HrsPairNaSegConst> tab;
-      std::vector<HrsPairSlot> slots;
-      PrematSubgConst c0;
-      int64_t items = 0, max_km = 0, panel_elems = 0;
-      CHECK(plan_hrs_table_pairwise(&t, &g, 1, tab, slots, &c0, &panel_elems, &items, &max_km) == DCOR_OK);
+      HrsPairTablePlan pl;
+      CHECK(plan_hrs_table_pairwise(&t, &g, 1, pl) == DCOR_OK);
+      const std::vector<HrsPairNaSegConst>& tab = pl.tab;
+      const std::vector<HrsPairSlot>& slots = pl.slots;
+      const int64_t max_km = pl.max_km, panel_elems = pl.panel_elems;
       CHECK(tab.size() == 1 && tab[0].n == c + 1 && tab[0].k == 2 && tab[0].m == 1 && max_km == 2);
       CHECK(tab[0].lr == dcor_lambda_receiver_from_noise(kLam[0], kLam[c], 2.0, 1.0 / (double)(c + 1)));
       CHECK(slots.size() == 1 && slots[0].n_ab == c + 1 && panel_elems == 16);
@@ -274,16 +236,13 @@ static void check_tiny_pairs() {
 }
 
 static void check_rejections() {
-  std::vector<HrsPairNaSegConst> tab;
-  std::vector<HrsPairSlot> slots;
-  PrematSubgConst c0;
-  int64_t items = 0, max_km = 0, panel_elems = 0;
+  HrsPairTablePlan pl;
+  const std::vector<HrsPairNaSegConst>& tab = pl.tab;
   dcor_hrs_pair_segment g;
   std::memset(&g, 0, sizeof(g));
   g.eps = 1.0; g.reps = 1; g.col_x = 0; g.col_y = 1;
   auto plan_n = [&](const dcor_hrs_table_na_desc& t, const dcor_hrs_pair_segment* s, int64_t ns) {
-    tab.clear(); slots.clear();
-    return plan_hrs_table_pairwise(&t, s, ns, tab, slots, &c0, &panel_elems, &items, &max_km);
+    return plan_hrs_table_pairwise(&t, s, ns, pl);
   };
   auto plan = [&](const dcor_hrs_table_na_desc& t, const dcor_hrs_pair_segment& s) { return plan_n(t, &s, 1); };
   const std::vector<uint64_t> full100(4 * 2, ~0ull);

@@ -3,50 +3,8 @@
 // with four distinct clip bounds; every record of the table planner must equal, as bytes over the
 // fields the two records share, the record plan_hrs_fused_sweep builds for the reference call of
 // the segment's pair (a panel on the two columns, lam_x = lam_s = lam[col_x], lam_y = lam_o =
-// lam[col_y]).  The segment arrays are heap blocks of exactly nseg elements, so a planner that
-// reads past its segments is caught when the program is built with a sanitizer.  Exit status 0:
-// every check held.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "dcor_plan.h"
-
-using namespace dcor;
-using namespace dcor::host;
-
-#define CHECK(cond)                                                        \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      std::fprintf(stderr, "%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #cond); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
-
-static std::string last_error() {
-  char buf[512];
-  dcor_last_error(buf, sizeof(buf));
-  return buf;
-}
-#define CHECK_FAILS(call, code, msg)                                       \
-  do {                                                                     \
-    CHECK((call) == (code));                                               \
-    if (last_error().find(msg) == std::string::npos) {                     \
-      std::fprintf(stderr, "%s:%d: message '%s'\n", __FILE__, __LINE__, last_error().c_str()); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
-
-template <class T>
-static std::unique_ptr<T[]> heap(const std::vector<T>& v) {   // exactly v.size() elements
-  std::unique_ptr<T[]> p(new T[v.size()]);
-  for (size_t i = 0; i < v.size(); ++i) p[i] = v[i];
-  return p;
-}
+// lam[col_y]).  Harness: check.h.
+#include "check.h"
 
 static const double* const kD = (const double*)4096;   // never dereferenced
 static const double kLam[4] = {1.75, 2.5, 3.0625, 0.9};
@@ -115,9 +73,11 @@ static void check_records(int64_t n) {
   for (const auto& reps : kReps) {
     const std::vector<dcor_hrs_pair_segment> segs = segments(reps);
     const auto hs = heap(segs);
-    std::vector<HrsPairSegConst> tab;
-    int64_t items = -1, max_km = -1;
-    CHECK(plan_hrs_table(&t, hs.get(), (int64_t)segs.size(), tab, &items, &max_km) == DCOR_OK);
+    HrsTablePlan pl;
+    pl.items = pl.max_km = -1;
+    CHECK(plan_hrs_table(&t, hs.get(), (int64_t)segs.size(), pl) == DCOR_OK);
+    const std::vector<HrsPairSegConst>& tab = pl.tab;
+    const int64_t items = pl.items, max_km = pl.max_km;
     size_t j = 0;
     int64_t first = 0, want_km = 0;
     for (size_t i = 0; i < reps.size(); ++i) {
@@ -138,6 +98,17 @@ static void check_records(int64_t n) {
     }
     CHECK(j == tab.size());
     CHECK(items == first && max_km == want_km);
+    CHECK(pl.lay.ok && pl.lay.bytes == HrsTableLayout(items, (int64_t)tab.size(), t.n, t.p).bytes);
+    // the call-wide constants: the first kept segment's reference call, no columns' addresses
+    for (size_t i = 0; i < reps.size(); ++i) {
+      if (reps[i] == 0) continue;
+      const dcor_premat_subg q = hrs_pair_desc(t, segs[i]);
+      PrematSubgConst want;
+      CHECK(premat_subg_const(&q, want) == DCOR_OK);
+      want.X = want.Y = nullptr;
+      CHECK(std::memcmp(&pl.c0, &want, sizeof(want)) == 0);
+      break;
+    }
   }
 }
 
@@ -149,9 +120,9 @@ static void check_geometry() {
     dcor_hrs_pair_segment g;
     std::memset(&g, 0, sizeof(g));
     g.eps = kEps[e]; g.reps = 1; g.col_x = 3; g.col_y = 1;
-    std::vector<HrsPairSegConst> tab;
-    int64_t items = 0, max_km = 0;
-    CHECK(plan_hrs_table(&t, &g, 1, tab, &items, &max_km) == DCOR_OK);
+    HrsTablePlan pl;
+    CHECK(plan_hrs_table(&t, &g, 1, pl) == DCOR_OK);
+    const std::vector<HrsPairSegConst>& tab = pl.tab;
     CHECK(tab.size() == 1 && tab[0].m == want_m[e] && tab[0].k == want_k[e]);
     // the constants that depend on lambda come from the segment's own columns
     const double ls = kLam[3], lo = kLam[1];
@@ -163,14 +134,12 @@ static void check_geometry() {
 }
 
 static void check_rejections() {
-  std::vector<HrsPairSegConst> tab;
-  int64_t items = 0, max_km = 0;
+  HrsTablePlan pl;
   dcor_hrs_pair_segment g;
   std::memset(&g, 0, sizeof(g));
   g.eps = 1.0; g.reps = 1; g.col_x = 0; g.col_y = 1;
   auto plan = [&](const dcor_hrs_table_desc& t, const dcor_hrs_pair_segment& s) {
-    tab.clear();
-    return plan_hrs_table(&t, &s, 1, tab, &items, &max_km);
+    return plan_hrs_table(&t, &s, 1, pl);
   };
   dcor_hrs_table_desc t = table_of(100, 100);
   t.D = nullptr;
@@ -214,7 +183,7 @@ static void check_rejections() {
   t = table_of(1, 1);
   CHECK_FAILS(plan(t, h), DCOR_EINVAL, "n must be in [2, 65536]");
   // a failed call reports no items
-  CHECK(items == 0 && max_km == 0);
+  CHECK(pl.items == 0 && pl.max_km == 0);
 }
 
 int main() {

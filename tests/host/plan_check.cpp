@@ -1,48 +1,6 @@
-// plan_check.cpp -- stand-alone check of the planning unit (csrc/dcor_plan.cpp), built from this
-// file and dcor_plan.cpp alone with a host compiler: no HIP, no device.  The segment arrays are
-// heap blocks of exactly nseg elements, so a planner that reads past its segments is caught when
-// the program is built with a sanitizer.  Exit status 0: every check held.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "dcor_plan.h"
-
-using namespace dcor;
-using namespace dcor::host;
-
-#define CHECK(cond)                                                        \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      std::fprintf(stderr, "%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #cond); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
-
-static std::string last_error() {
-  char buf[512];
-  dcor_last_error(buf, sizeof(buf));
-  return buf;
-}
-#define CHECK_FAILS(call, code, msg)                                       \
-  do {                                                                     \
-    CHECK((call) == (code));                                               \
-    if (last_error() != (msg)) {                                           \
-      std::fprintf(stderr, "%s:%d: message '%s'\n", __FILE__, __LINE__, last_error().c_str()); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
-
-template <class T>
-static std::unique_ptr<T[]> heap(const std::vector<T>& v) {   // exactly v.size() elements
-  std::unique_ptr<T[]> p(new T[v.size()]);
-  for (size_t i = 0; i < v.size(); ++i) p[i] = v[i];
-  return p;
-}
+// plan_check.cpp -- stand-alone check of the planning unit (csrc/dcor_plan.cpp): the sign and HRS
+// sweep planners' tables against direct calls of the constant builders (harness: check.h).
+#include "check.h"
 
 static const double* const kX = (const double*)64;   // never dereferenced
 static const double* const kY = (const double*)128;
@@ -100,11 +58,14 @@ static void check_sign(int64_t n, int64_t p) {
     td.nsim = 1000;
     const auto ha = heap(a);
     const auto hb = heap(b);
-    std::vector<SignSegConst> ta;
-    std::vector<SignPairSegConst> tb;
-    int64_t ia = -1, ib = -1;
-    CHECK(plan_sign_panel(&pd, ha.get(), (int64_t)a.size(), ta, &ia) == DCOR_OK);
-    CHECK(plan_sign_table(&td, hb.get(), (int64_t)b.size(), tb, &ib) == DCOR_OK);
+    SignPanelPlan pa;
+    SignTablePlan pb;
+    pa.items = pb.items = -1;
+    CHECK(plan_sign_panel(&pd, ha.get(), (int64_t)a.size(), pa) == DCOR_OK);
+    CHECK(plan_sign_table(&td, hb.get(), (int64_t)b.size(), pb) == DCOR_OK);
+    const std::vector<SignSegConst>& ta = pa.tab;
+    const std::vector<SignPairSegConst>& tb = pb.tab;
+    const int64_t ia = pa.items, ib = pb.items;
     size_t j = 0;
     int64_t first = 0;
     for (size_t i = 0; i < reps.size(); ++i) {
@@ -121,6 +82,9 @@ static void check_sign(int64_t n, int64_t p) {
     }
     CHECK(j == ta.size() && j == tb.size());
     CHECK(ia == first && ib == first);
+    // the scratch is the plan's own: built once, for the kept segments
+    CHECK(pa.lay.ok && pa.lay.bytes == SignPanelLayout((int64_t)ta.size(), n).bytes);
+    CHECK(pb.lay.ok && pb.lay.bytes == SignTableLayout((int64_t)tb.size(), n, p).bytes);
   }
 }
 
@@ -217,15 +181,14 @@ static void check_rejections() {
     std::memset(&b[0], 0, sizeof(b[0]));
     b[0].eps1 = b[0].eps2 = 1.0; b[0].reps = 1;
     const auto hb = heap(b);
-    std::vector<SignPairSegConst> tb;
-    int64_t items = 0;
-    CHECK_FAILS(plan_sign_table(&td, hb.get(), 1, tb, &items), DCOR_EINVAL,
+    SignTablePlan tb;
+    CHECK_FAILS_EXACT(plan_sign_table(&td, hb.get(), 1, tb), DCOR_EINVAL,
                 "sign_table: p * npad * 8 scratch bytes overflow (p = 2147483647, n = 2147483647)");
     td.n = 100; td.p = 3; td.ld = 99;
-    CHECK_FAILS(plan_sign_table(&td, hb.get(), 1, tb, &items), DCOR_EINVAL, "sign_table: ld = 99 < n = 100");
+    CHECK_FAILS_EXACT(plan_sign_table(&td, hb.get(), 1, tb), DCOR_EINVAL, "sign_table: ld = 99 < n = 100");
     td.ld = 100; b[0].col_y = 3;
     const auto hc = heap(b);
-    CHECK_FAILS(plan_sign_table(&td, hc.get(), 1, tb, &items), DCOR_EINVAL,
+    CHECK_FAILS_EXACT(plan_sign_table(&td, hc.get(), 1, tb), DCOR_EINVAL,
                 "sign_table: segment 0: columns (0, 3) outside [0, 3)");
   }
   // the HRS sweeps' panel and base checks, and their place among the segment checks
@@ -252,25 +215,25 @@ static void check_rejections() {
     const dcor_panel pn = panel_of(c.X, c.Y, c.n);
     HrsFusedSweepPlan f;
     HrsSweepPlan m;
-    CHECK_FAILS(plan_hrs_fused_sweep(&d, &pn, ok.get(), 2, f), DCOR_EINVAL,
+    CHECK_FAILS_EXACT(plan_hrs_fused_sweep(&d, &pn, ok.get(), 2, f), DCOR_EINVAL,
                 std::string("hrs_fused_sweep: ") + c.msg);
-    CHECK_FAILS(plan_hrs_sweep(&d, &pn, ok.get(), 2, m), DCOR_EINVAL, std::string("hrs_sweep: ") + c.msg);
+    CHECK_FAILS_EXACT(plan_hrs_sweep(&d, &pn, ok.get(), 2, m), DCOR_EINVAL, std::string("hrs_sweep: ") + c.msg);
     // with a bad segment too: the fused sweep reports the segment, the materialised one the panel
     HrsFusedSweepPlan f2;
     HrsSweepPlan m2;
-    CHECK_FAILS(plan_hrs_fused_sweep(&d, &pn, bad.get(), 2, f2), DCOR_EINVAL,
+    CHECK_FAILS_EXACT(plan_hrs_fused_sweep(&d, &pn, bad.get(), 2, f2), DCOR_EINVAL,
                 "hrs_fused_sweep: segment 1: need eps > 0, reps, rep_begin, out_row >= 0");
-    CHECK_FAILS(plan_hrs_sweep(&d, &pn, bad.get(), 2, m2), DCOR_EINVAL, std::string("hrs_sweep: ") + c.msg);
+    CHECK_FAILS_EXACT(plan_hrs_sweep(&d, &pn, bad.get(), 2, m2), DCOR_EINVAL, std::string("hrs_sweep: ") + c.msg);
   }
   dcor_premat_subg d = base;
   d.xy_stride = 100;
   const dcor_panel pn = panel_of(kX, kY, 100);
   HrsFusedSweepPlan f;
-  CHECK_FAILS(plan_hrs_fused_sweep(&d, &pn, ok.get(), 2, f), DCOR_EINVAL,
+  CHECK_FAILS_EXACT(plan_hrs_fused_sweep(&d, &pn, ok.get(), 2, f), DCOR_EINVAL,
               "hrs_fused_sweep: X, Y, n must be the panel's and xy_stride 0");
   // a bad segment is reported before the panel is read: no panel needed
   HrsFusedSweepPlan f2;
-  CHECK_FAILS(plan_hrs_fused_sweep(&base, (const dcor_panel*)8, bad.get(), 2, f2), DCOR_EINVAL,
+  CHECK_FAILS_EXACT(plan_hrs_fused_sweep(&base, (const dcor_panel*)8, bad.get(), 2, f2), DCOR_EINVAL,
               "hrs_fused_sweep: segment 1: need eps > 0, reps, rep_begin, out_row >= 0");
 }
 

@@ -2,50 +2,8 @@
 // from this file and dcor_plan.cpp alone with a host compiler: no HIP, no device.  Every record of
 // the planner must equal, as bytes, the fields make_subg yields for the segment's (n, eta1, eta2,
 // eps1, eps2) with hrs = 0 and no override, and the list of distinct batch sizes must be the
-// segments'.  The segment arrays are heap blocks of exactly nseg elements, so a planner that reads
-// past its segments is caught when the program is built with a sanitizer.  Exit status 0: every
-// check held.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "dcor_plan.h"
-
-using namespace dcor;
-using namespace dcor::host;
-
-#define CHECK(cond)                                                        \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      std::fprintf(stderr, "%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #cond); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
-
-static std::string last_error() {
-  char buf[512];
-  dcor_last_error(buf, sizeof(buf));
-  return buf;
-}
-#define CHECK_FAILS(call, code, msg)                                       \
-  do {                                                                     \
-    CHECK((call) == (code));                                               \
-    if (last_error().find(msg) == std::string::npos) {                     \
-      std::fprintf(stderr, "%s:%d: message '%s'\n", __FILE__, __LINE__, last_error().c_str()); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
-
-template <class T>
-static std::unique_ptr<T[]> heap(const std::vector<T>& v) {   // exactly v.size() elements
-  std::unique_ptr<T[]> p(new T[v.size()]);
-  for (size_t i = 0; i < v.size(); ++i) p[i] = v[i];
-  return p;
-}
+// segments'.  Harness: check.h.
+#include "check.h"
 
 static const double* const kX = (const double*)4096;   // never dereferenced
 static const double* const kY = (const double*)8192;
@@ -95,11 +53,13 @@ static void check_list(int64_t n, double eta1, double eta2, const std::vector<in
   std::vector<dcor_subg_segment> segs;
   for (size_t i = 0; i < 7; ++i) segs.push_back(seg_of(e[i][0], e[i][1], reps[i], i));
   const auto hs = heap(segs);
-  std::vector<SubgSegConst> tab;
-  std::vector<SubgMeanSlot> slots;
-  SubgConst c0;
-  int64_t items = -1;
-  CHECK(plan_subg_panel(&p, hs.get(), 7, tab, slots, &c0, &items) == DCOR_OK);
+  SubgPanelPlan pl;
+  pl.items = -1;
+  CHECK(plan_subg_panel(&p, hs.get(), 7, pl) == DCOR_OK);
+  const std::vector<SubgSegConst>& tab = pl.tab;
+  const std::vector<SubgMeanSlot>& slots = pl.slots;
+  const SubgConst& c0 = pl.c0;
+  const int64_t items = pl.items;
   CHECK(tab.size() == 6 && items == 17);
   CHECK(slots.size() == want_m.size());
   int64_t off = 0;
@@ -129,17 +89,14 @@ static void check_list(int64_t n, double eta1, double eta2, const std::vector<in
   reference_record(p, segs[0], 0, 0, 0, &a0);
   CHECK(std::memcmp(&c0, &a0, sizeof(SubgConst)) == 0);
   CHECK(c0.l1 == dcor_lambda_n((double)n, eta1) && c0.l2 == dcor_lambda_n((double)n, eta2));
+  CHECK(pl.lay.ok && pl.lay.bytes == SubgPanelLayout((int64_t)tab.size(), (int64_t)slots.size(), off, n).bytes);
 }
 
 static void check_rejections() {
-  std::vector<SubgSegConst> tab;
-  std::vector<SubgMeanSlot> slots;
-  SubgConst c0;
-  int64_t items = 0;
+  SubgPanelPlan pl;
   const dcor_subg_segment g = seg_of(1.0, 1.0, 1, 0);
   auto plan = [&](const dcor_subg_panel_desc& p, const dcor_subg_segment& s) {
-    tab.clear(); slots.clear();
-    return plan_subg_panel(&p, &s, 1, tab, slots, &c0, &items);
+    return plan_subg_panel(&p, &s, 1, pl);
   };
   dcor_subg_panel_desc p = panel_of(100, 1, 1);
   p.X = nullptr;
@@ -189,12 +146,11 @@ static void check_rejections() {
     std::vector<dcor_subg_segment> v = {g, g, g};
     v[2].reps = -1;
     const auto hv = heap(v);
-    tab.clear(); slots.clear();
     p = panel_of(100, 1, 1);
-    CHECK_FAILS(plan_subg_panel(&p, hv.get(), 3, tab, slots, &c0, &items), DCOR_EINVAL, "segment 2:");
+    CHECK_FAILS(plan_subg_panel(&p, hv.get(), 3, pl), DCOR_EINVAL, "segment 2:");
     v[2].reps = 0x40000000LL; v[1].reps = 0x40000000LL;
     const auto hw = heap(v);
-    CHECK_FAILS(plan_subg_panel(&p, hw.get(), 3, tab, slots, &c0, &items), DCOR_EINVAL, "2^31 - 1");
+    CHECK_FAILS(plan_subg_panel(&p, hw.get(), 3, pl), DCOR_EINVAL, "2^31 - 1");
   }
 }
 

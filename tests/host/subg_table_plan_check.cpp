@@ -1,54 +1,12 @@
 // subg_table_plan_check.cpp -- stand-alone check of plan_subg_table and SubgTableLayout
-// (csrc/dcor_plan.cpp, csrc/dcor_engine.h), built from this file and dcor_plan.cpp alone with a host
+// (csrc/dcor_plan.cpp, csrc/dcor_layout.h), built from this file and dcor_plan.cpp alone with a host
 // compiler: no HIP, no device.  Every kept record of the planner must equal, as bytes over its
 // SubgSegConst part, the record plan_subg_panel builds for the segment's reference call (X = column
 // col_x, Y = column col_y, eta1 = eta[col_x], eta2 = eta[col_y]) once the place fields (first,
 // out_row, m_slot, mean_off) are set alike; the slot list must be the segments' distinct m in order
 // of first use; the clips must be the reference calls' l1 / l2 bits; the layout's regions must not
-// overlap.  The segment and eta arrays are heap blocks of exactly their length, so a planner that
-// reads past them is caught when the program is built with a sanitizer.  Exit status 0: every check
-// held.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "dcor_plan.h"
-
-using namespace dcor;
-using namespace dcor::host;
-
-#define CHECK(cond)                                                        \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      std::fprintf(stderr, "%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #cond); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
-
-static std::string last_error() {
-  char buf[512];
-  dcor_last_error(buf, sizeof(buf));
-  return buf;
-}
-#define CHECK_FAILS(call, code, msg)                                       \
-  do {                                                                     \
-    CHECK((call) == (code));                                               \
-    if (last_error().find(msg) == std::string::npos) {                     \
-      std::fprintf(stderr, "%s:%d: message '%s'\n", __FILE__, __LINE__, last_error().c_str()); \
-      std::exit(1);                                                        \
-    }                                                                      \
-  } while (0)
-
-template <class T>
-static std::unique_ptr<T[]> heap(const std::vector<T>& v) {   // exactly v.size() elements
-  std::unique_ptr<T[]> p(new T[v.size()]);
-  for (size_t i = 0; i < v.size(); ++i) p[i] = v[i];
-  return p;
-}
+// overlap.  Harness: check.h.
+#include "check.h"
 
 static const double* const kD = (const double*)4096;   // never dereferenced
 
@@ -84,12 +42,11 @@ static SubgSegConst reference_record(const dcor_subg_table_desc& t, const dcor_s
   std::memset(&s, 0, sizeof(s));
   s.eps1 = g.eps1; s.eps2 = g.eps2; s.seed = g.seed; s.rep_begin = g.rep_begin; s.reps = g.reps;
   s.out_row = g.out_row;
-  std::vector<SubgSegConst> tab;
-  std::vector<SubgMeanSlot> slots;
-  int64_t items = 0;
-  CHECK(plan_subg_panel(&p, &s, 1, tab, slots, c0, &items) == DCOR_OK);
-  CHECK(tab.size() == 1 && slots.size() == 1 && items == g.reps);
-  return tab[0];
+  SubgPanelPlan pl;
+  CHECK(plan_subg_panel(&p, &s, 1, pl) == DCOR_OK);
+  CHECK(pl.tab.size() == 1 && pl.slots.size() == 1 && pl.items == g.reps);
+  *c0 = pl.c0;
+  return pl.tab[0];
 }
 
 // Pairs, (a, a), (b, a), a zero-rep segment, per-column eta; m = 8 shared by two segments on
@@ -105,12 +62,14 @@ static void check_list(int64_t n, const std::vector<int64_t>& want_m) {
   std::vector<dcor_subg_pair_segment> segs;
   for (size_t i = 0; i < 8; ++i) segs.push_back(seg_of(col[i][0], col[i][1], e[i][0], e[i][1], reps[i], i));
   const auto hs = heap(segs);
-  std::vector<SubgPairSegConst> tab;
-  std::vector<SubgMeanSlot> slots;
-  std::vector<double> clips;
-  SubgConst c0;
-  int64_t items = -1;
-  CHECK(plan_subg_table(&t, hs.get(), 8, tab, slots, clips, &c0, &items) == DCOR_OK);
+  SubgTablePlan pl;
+  pl.items = -1;
+  CHECK(plan_subg_table(&t, hs.get(), 8, pl) == DCOR_OK);
+  const std::vector<SubgPairSegConst>& tab = pl.tab;
+  const std::vector<SubgMeanSlot>& slots = pl.slots;
+  const std::vector<double>& clips = pl.clips;
+  const SubgConst& c0 = pl.c0;
+  const int64_t items = pl.items;
   CHECK(tab.size() == 7 && items == 19);
   CHECK(slots.size() == want_m.size());
   int64_t off = 0;
@@ -154,6 +113,7 @@ static void check_list(int64_t n, const std::vector<int64_t>& want_m) {
   // the layout: regions in order, disjoint, aligned as stated
   const int64_t nmeans = off;
   const SubgTableLayout lay((int64_t)tab.size(), (int64_t)slots.size(), nmeans, n, p);
+  CHECK(pl.lay.ok && pl.lay.cols_off == lay.cols_off && pl.lay.bytes == lay.bytes);   // the plan's own scratch
   CHECK(lay.ok && lay.npad % 4 == 0 && lay.npad >= n && lay.npad < n + 4);
   CHECK(lay.mpitch % 2 == 0 && lay.mpitch >= nmeans && lay.mpitch < nmeans + 2);
   CHECK(lay.tab_off == 0);
@@ -186,26 +146,20 @@ static void check_layout_overflow() {
   const auto eta = heap(one);
   const dcor_subg_table_desc t = table_of(big, big, big, eta.get());
   const dcor_subg_pair_segment g = seg_of(0, 0, 1, 1, 1, 0);
-  std::vector<SubgPairSegConst> tab;
-  std::vector<SubgMeanSlot> slots;
-  std::vector<double> clips;
-  SubgConst c0;
-  int64_t items = 0;
-  CHECK_FAILS(plan_subg_table(&t, &g, 1, tab, slots, clips, &c0, &items), DCOR_EINVAL, "scratch bytes overflow");
+  SubgTablePlan pl;
+  CHECK_FAILS(plan_subg_table(&t, &g, 1, pl), DCOR_EINVAL, "scratch bytes overflow");
 }
 
 static void check_rejections() {
-  std::vector<SubgPairSegConst> tab;
-  std::vector<SubgMeanSlot> slots;
-  std::vector<double> clips;
-  SubgConst c0;
-  int64_t items = 0;
+  SubgTablePlan pl;
+  const std::vector<SubgPairSegConst>& tab = pl.tab;
+  const std::vector<SubgMeanSlot>& slots = pl.slots;
+  const std::vector<double>& clips = pl.clips;
   const std::vector<double> good_v = {1.0, 0.5, 0.8};
   const auto good = heap(good_v);
   const dcor_subg_pair_segment g = seg_of(0, 1, 1.0, 1.0, 1, 0);
   auto plan = [&](const dcor_subg_table_desc& t, const dcor_subg_pair_segment& s) {
-    tab.clear(); slots.clear(); clips.clear();
-    return plan_subg_table(&t, &s, 1, tab, slots, clips, &c0, &items);
+    return plan_subg_table(&t, &s, 1, pl);
   };
   auto T = [&](const double* eta = nullptr) { return table_of(100, 3, 100, eta ? eta : good.get()); };
   dcor_subg_table_desc t = T();
@@ -288,17 +242,15 @@ static void check_rejections() {
     std::vector<dcor_subg_pair_segment> v = {g, g, g};
     v[2].col_y = 3;
     const auto hv = heap(v);
-    tab.clear(); slots.clear(); clips.clear();
     t = T();
-    CHECK_FAILS(plan_subg_table(&t, hv.get(), 3, tab, slots, clips, &c0, &items), DCOR_EINVAL, "segment 2: columns");
+    CHECK_FAILS(plan_subg_table(&t, hv.get(), 3, pl), DCOR_EINVAL, "segment 2: columns");
     v[2].col_y = 1; v[2].reps = 0x40000000LL; v[1].reps = 0x40000000LL;
     const auto hw = heap(v);
-    CHECK_FAILS(plan_subg_table(&t, hw.get(), 3, tab, slots, clips, &c0, &items), DCOR_EINVAL, "2^31 - 1");
+    CHECK_FAILS(plan_subg_table(&t, hw.get(), 3, pl), DCOR_EINVAL, "2^31 - 1");
     v[0].reps = v[1].reps = v[2].reps = 0;
     const auto hz = heap(v);
-    tab.clear(); slots.clear(); clips.clear();
-    CHECK(plan_subg_table(&t, hz.get(), 3, tab, slots, clips, &c0, &items) == DCOR_OK);
-    CHECK(tab.empty() && slots.empty() && clips.empty() && items == 0);
+    CHECK(plan_subg_table(&t, hz.get(), 3, pl) == DCOR_OK);
+    CHECK(tab.empty() && slots.empty() && clips.empty() && pl.items == 0);
   }
 }
 
