@@ -334,13 +334,33 @@ __device__ __forceinline__ DD dd_div_d(DD a, double b) {
 }
 __device__ __forceinline__ DD dd_neg(DD a) { return DD{-a.hi, -a.lo}; }
 
-// sample variance (n-1) from double-double sum and sum of squares
+// sample variance (n-1) from double-double sum and sum of squares.  The callers round each square to
+// double before it enters s2, so on (nearly) constant input the numerator is rounding residue of
+// either sign, where R's two-pass var gives 0 on a constant (and the HRS interval branches on
+// sd == 0, real-data-sims.R:237-238).
+//  - The sums of a constant sample are recognised exactly.  n copies of q give s1 = n q and
+//    s2 = n fl(q q) with no rounding at all: every partial sum is a multiple of q's (of fl(q q)'s)
+//    last bit below 2^106 of it, which the compensated adds and the fold steps of the reductions
+//    keep exactly (two_sum is error-free and the low parts' plain adds are exact on such
+//    multiples); a pair's fl(q q) + fl(q q), and a zero pad's q q + 0, change nothing.  So with
+//    q = fl(s1 / n), s1 == n q and s2 == n fl(q q) as normalised double-doubles mean the sample
+//    cannot be told from a constant, and the variance is 0.  Any other sample with these two sums
+//    has a variance below the rounding of its squares, 2 * 2^-53 * s2 / (n - 1).
+//  - Otherwise a negative value is 0 (R's var is never negative; the callers take sqrt).
+// A NaN stays NaN.
 __device__ __forceinline__ double dd_var(DD s1, DD s2, double n) {
   if (!(n >= 2)) return dnan();
   const DD mean = dd_div_d(s1, n);
+  {
+    const double q = mean.hi + mean.lo;
+    const DD a1 = two_sum(s1.hi, s1.lo), a2 = two_sum(s2.hi, s2.lo);
+    const DD c1 = two_prod(n, q), c2 = two_prod(n, q * q);
+    if (a1.hi == c1.hi && a1.lo == c1.lo && a2.hi == c2.hi && a2.lo == c2.lo) return 0.0;
+  }
   const DD c = dd_add(s2, dd_neg(dd_mul(s1, mean)));
   const DD v = dd_div_d(c, n - 1.0);
-  return v.hi + v.lo;
+  const double var = v.hi + v.lo;
+  return var < 0.0 ? 0.0 : var;
 }
 
 // ------------------------------------------------------------ reductions
