@@ -668,6 +668,35 @@ def hrs_table(R, p=8, arm="both"):
         print(json.dumps({"config": "HT-check", "records_bit_equal": same}), flush=True)
 
 
+def hrs_private(R, p=8):
+    """HTP: HT-table's shape (n = 19,433, p columns, the p (p - 1) / 2 pairs x 23 eps x R sweep, the
+    same keys) on the raw table with the private standardisation drawn per replicate, in one
+    dcor_hrs_private_table_launch call.  Column c of the raw table is 60 + 10 z_c clipped to [30, 90].
+    Its rate stands next to HT-table's, which runs the correlation stage alone on one frozen table.
+    Not in the default list: reach it with --only HTP."""
+    import numpy as np
+    import torch
+    from dcor import hrs, signpanel
+    raw = np.asfortranarray(60.0 + 10.0 * signpanel.standin_table(19433, p, 0.3))
+    bounds = [(30.0, 90.0)] * p
+    pairs = signpanel.all_pairs(p)
+    ne = len(hrs.EPS_GRID)
+    segs = [(a, b, e, 10 + 1000 * (j * ne + idx), 20 + 1000 * (j * ne + idx), 0, R)
+            for j, (a, b) in enumerate(pairs) for idx, e in enumerate(hrs.EPS_GRID, start=1)]
+    total = len(segs) * R
+    hrs.private_segments(raw, bounds, segs)    # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = hrs.private_segments(raw, bounds, segs)
+    torch.cuda.synchronize()
+    t = time.perf_counter() - t0
+    line("HTP", n=int(raw.shape[0]), p=p, pairs=len(pairs), replicates=total, seconds=t, reps_per_s=total / t,
+         finite=bool(np.isfinite(res).all()),
+         kernel="k_hrs_private_prep + k_hrs_private_table + k_hrs_private_epilogue",
+         note="host wall time of one call: table upload, one preparation launch over the columns, one streaming "
+              "and one epilogue launch over every (pair, eps) segment, records copied back")
+
+
 def hrs_table_na(R, p=4, gap=0.2, repeats=5):
     """HTN: the HRS estimators on the pairwise-complete cases of a p-column stand-in table (n =
     19,433, C5's row count) with about `gap` of every column's rows missing independently: the p (p -
@@ -1039,6 +1068,7 @@ def main():
     if "HT-table" in which: hrs_table(a.hs_R, arm="table")
     if "HT-pairs" in which: hrs_table(a.hs_R, arm="pairs")
     if "HTN" in which: hrs_table_na(a.hs_R)
+    if "HTP" in which: hrs_private(a.hs_R)
     if "S" in which: subg()
     if "R1" in which: rstream_c1()
     if "RG" in which: rstream_grid()

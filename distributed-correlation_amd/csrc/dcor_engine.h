@@ -5,6 +5,7 @@
 // the host with the R operation order (see dcor_capi.cpp) and handed to the kernel by
 // value, so the per-replicate kernel only does the data-dependent arithmetic.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #include <climits>
@@ -373,6 +374,80 @@ int launch_hrs_pair_table(const PrematSubgConst& c, const double* D, int64_t n, 
                           const uint64_t* masks, int64_t nw, const HrsPairSlot* slots, int nslot,
                           double2* panels, const HrsPairNaSegConst* tab, int nseg, int64_t items,
                           int64_t max_km, void* part, dcor_rep_out* out, void* stream);
+
+// ---- HRS table replicates with the private standardisation drawn per replicate
+// (dcor_hrs_private_table_launch) ----
+// The two derivations a replicate of that entry makes on the device and the host pins: plain IEEE
+// arithmetic (+ - * / sqrt, compares) in one fixed order, marked for host and device, so under
+// -ffp-contract=off both sides give the same bits (tests/host/hrs_private_plan_check.cpp compares
+// them with what plan_hrs_table writes, field by field).  No log: log(1 / delta) differs between
+// the host's and the device's libm and is carried in the segment record instead.
+
+// R's max(a, b): NaN when either is (r_max on the host, rmax on the device).
+__host__ __device__ inline double hrs_nanmax(double a, double b) {
+  return (a != a || b != b) ? __builtin_nan("") : (a > b ? a : b);
+}
+// A column's private release from the means m1, m2 of its clipped sample and its squares and the
+// two unit Laplace draws: dp_sd (real-data-sims.R:73-84: k_dp_sd's mu, m2p and sd with dcor_dp_sd's
+// two scales), standardize_dp's denominator max(sd, 1e-8) (:89) and lambda_from_priv (:104).
+struct HrsPriv { double mean, sd, den, lam; };
+__host__ __device__ inline HrsPriv hrs_private_release(double m1, double m2, double lo, double hi, double nd,
+                                                       double eps_mean, double eps_m2, double lap0,
+                                                       double lap1) {
+  const double s_mu = (hi - lo) / (nd * eps_mean);           // :69
+  const double s_m2 = (hi * hi - lo * lo) / (nd * eps_m2);   // :80
+  HrsPriv r;
+  r.mean = m1 + s_mu * lap0;
+  const double m2p = m2 + s_m2 * lap1;
+  r.sd = sqrt(hrs_nanmax(m2p - r.mean * r.mean, 0.0));
+  r.den = hrs_nanmax(r.sd, 1e-8);
+  r.lam = hrs_nanmax(fabs((lo - r.mean) / r.den), fabs((hi - r.mean) / r.den));
+  return r;
+}
+// lambda_receiver_from_noise (real-data-sims.R:172) from log(1 / delta).
+__host__ __device__ inline double hrs_lambda_receiver(double lam_s, double lam_o, double eps_s,
+                                                      double log_inv_delta) {
+  const double b_s = 2.0 * lam_s / eps_s;
+  return (lam_s + b_s * log_inv_delta) * lam_o;
+}
+// What make_subg derives from the clip bounds of an HRS table segment (X = the sender, eps1 = eps2 =
+// eps, lam_x = lam_s = lx, lam_y = lam_o = ly, lam_r = lambda_receiver_from_noise): the fields of
+// HrsSegConst that depend on lambda.  crit_sqrt2: make_subg's crit * sqrt(2.0), the host's.
+struct HrsLamConst { double bx, by, bs, lr, s_central, sn2x2, crit_sqrt2_s; };
+__host__ __device__ inline HrsLamConst hrs_lambda_consts(double lx, double ly, double eps, double md, double nd,
+                                                         double log_inv_delta, double crit_sqrt2) {
+  HrsLamConst c;
+  c.bx = 2.0 * lx / (md * eps);                                // ver-cor-subG.R:48
+  c.by = 2.0 * ly / (md * eps);                                // :49
+  c.lr = hrs_lambda_receiver(lx, ly, eps, log_inv_delta);
+  c.bs = 2.0 * lx / (eps);                                     // :89
+  c.s_central = 2.0 * c.lr / (nd * eps);                       // :91
+  c.sn2x2 = 2.0 * (c.s_central * c.s_central);                 // :99
+  c.crit_sqrt2_s = crit_sqrt2 * (2.0 * c.lr / (nd * eps));     // real-data-sims.R:238
+  return c;
+}
+// A table segment of that entry: the lambda-dependent fields of HrsSegConst (bx, by, bs, lr,
+// s_central, sn2x2, crit_sqrt2_s) are zero in the table -- every replicate derives its own with
+// hrs_lambda_consts -- and the two host-only factors of that derivation ride along.
+struct HrsPrivSegConst : HrsPairSegConst {
+  double log_inv_delta;   // std::log(1.0 / delta)
+  double crit_sqrt2;      // crit * std::sqrt(2.0)
+};
+static_assert(sizeof(HrsPrivSegConst) == 184, "the private table entry's device table stride");
+// The call-wide part of the standardisation: budgets and the Philox key of DCOR_SITE_STD.
+struct HrsPrivCall {
+  double eps_mean, eps_m2;
+  uint32_t k0, k1;
+};
+// The preparation launch (one workgroup per column c of D: m12[2 c], m12[2 c + 1] = k_dp_sd's means of
+// the column clipped to [lohi[2 c], lohi[2 c + 1]] and of its squares; the clipped column to cols at
+// pitch npad, zeros from n on), then the streaming and epilogue launches over `items` replicates of
+// the nseg >= 1 segments in `tab` (device), as launch_hrs_table.  c: n, nd, sqrt_n, crit, mix, hrs.
+// priv: null, or 6 doubles per record (mean, sd, lam of X, then of Y) at the records' rows.
+int launch_hrs_private_table(const PrematSubgConst& c, const HrsPrivCall& pv, const double* D, int64_t p,
+                             int64_t ld, const double* lohi, double* m12, double* cols, int64_t npad,
+                             const HrsPrivSegConst* tab, int nseg, int64_t items, int64_t max_km, void* part,
+                             dcor_rep_out* out, double* priv, void* stream);
 
 // ---- sub-G simulation estimators on a shared panel (dcor_subg_panel_launch; dcor_subgpanel.hip) ----
 // One segment of a sub-G panel call: the part of SubgConst that depends on the segment's (eps1,

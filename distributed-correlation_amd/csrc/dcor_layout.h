@@ -131,6 +131,27 @@ struct HrsTableLayout : Carver {
   double* cols(void* base) const { return (double*)((char*)base + cols_off); }
 };
 
+// Private HRS-table scratch: partials (one SubgPartial per replicate of the call) | the segment table
+// | the p clip intervals (lo, hi) | the p pairs (m1, m2) the preparation writes | the p raw columns
+// clipped to their intervals, laid out as HrsTableLayout's.
+struct HrsPrivateLayout : Carver {
+  int64_t npad = 0;
+  size_t tab_off = 0, lohi_off = 0, m12_off = 0, cols_off = 0;
+  HrsPrivateLayout(int64_t items = 0, int64_t nseg = 0, int64_t n = 0, int64_t p = 0)
+      : Carver(n >= 1 && p >= 1), npad((n + 3) & ~(int64_t)3) {
+    add(items, sizeof(SubgPartial));
+    tab_off = add(nseg, sizeof(HrsPrivSegConst));
+    lohi_off = add(p, 2 * sizeof(double));
+    m12_off = add(p, 2 * sizeof(double));
+    cols_off = add({p, npad}, sizeof(double));
+  }
+  static HrsPrivateLayout columns(int64_t n, int64_t p) { return HrsPrivateLayout(0, 0, n, p); }
+  HrsPrivSegConst* tab(void* base) const { return (HrsPrivSegConst*)((char*)base + tab_off); }
+  double* lohi(void* base) const { return (double*)((char*)base + lohi_off); }
+  double* m12(void* base) const { return (double*)((char*)base + m12_off); }
+  double* cols(void* base) const { return (double*)((char*)base + cols_off); }
+};
+
 // Pairwise HRS-table scratch: partials (one SubgPartial per replicate of the call) | the segment
 // table, then the slot table | the p clip bounds | the p masks of nw = ceil(n / 64) words | the
 // slots' packed panels (panel_elems double2 in all).

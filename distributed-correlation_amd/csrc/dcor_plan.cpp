@@ -1,6 +1,6 @@
 // dcor_plan.cpp -- the device-free half of the host side (dcor_plan.h): the error reporter, the
 // argument checks of the reference's stopifnot() calls, every data-independent scalar of the
-// estimators (R operation order, cited), and the segment planners of the eight segment-list
+// estimators (R operation order, cited), and the segment planners of the nine segment-list
 // entries.  No HIP: this file and the headers it includes compile with a host compiler alone.
 #include "dcor_plan.h"
 
@@ -524,6 +524,69 @@ int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* se
   return DCOR_OK;
 }
 
+int plan_hrs_private(const dcor_hrs_private_desc* t, const dcor_hrs_pair_segment* segs, int64_t nseg,
+                     HrsPrivatePlan& plan) {
+  const char* const entry = "hrs_private_table";
+  plan = HrsPrivatePlan();
+  if (!t->D || !t->lo || !t->hi) return fail(DCOR_EINVAL, "%s: null argument (D, lo, hi)", entry);
+  if (t->n < 2 || t->n > DCOR_DICT_NMAX)
+    return fail(DCOR_EINVAL, "%s: n must be in [2, %d] (got %lld): the kernel keeps a replicate's "
+                "u16 batch indices in LDS and there is no fallback for a larger table", entry, DCOR_DICT_NMAX,
+                (long long)t->n);
+  if (int st = table_shape(entry, *t)) return st;
+  if (!HrsPrivateLayout::columns(t->n, t->p).ok)
+    return fail(DCOR_EINVAL, "%s: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)", entry,
+                (long long)t->p, (long long)t->n);
+  if ((uintptr_t)t->D & 7) return fail(DCOR_EINVAL, "%s: D must be aligned to 8 bytes", entry);
+  for (int64_t c = 0; c < t->p; ++c)
+    if (!std::isfinite(t->lo[c]) || !std::isfinite(t->hi[c]) || !(t->lo[c] < t->hi[c]))
+      return fail(DCOR_EINVAL, "%s: column %lld: need finite lo < hi (got %g, %g)", entry, (long long)c,
+                  t->lo[c], t->hi[c]);
+  if (!std::isfinite(t->eps_mean) || !std::isfinite(t->eps_m2) || !(t->eps_mean > 0.0) || !(t->eps_m2 > 0.0))
+    return fail(DCOR_EINVAL, "%s: eps_mean, eps_m2 must be finite and > 0 (got %g, %g)", entry, t->eps_mean,
+                t->eps_m2);
+  if (!(t->delta > 0.0)) return fail(DCOR_EINVAL, "%s: delta must be positive", entry);
+  if (int st = check_alpha_nsim(t->n, t->alpha, t->nsim)) return st;
+  if (int st = segment_heads(entry, segs, nseg, t->p, &plan.items)) return st;
+  const double log_inv_delta = std::log(1.0 / t->delta);   // lambda_receiver_from_noise's, rds:172
+  int64_t first = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_hrs_pair_segment& g = segs[i];
+    // make_subg's checks and everything of it that no clip bound enters; the bounds are placeholders
+    PrematSubgConst pc;
+    std::memset(&pc, 0, sizeof(pc));
+    if (int st = make_subg(t->n, g.eps, g.eps, 1.0, 1.0, t->alpha, 1, 1.0, 1.0, 1.0, 1.0, 1.0, t->delta,
+                           t->nsim, pc.s, &pc.lo_, &pc.crit_sqrt2_s))
+      return st;
+    if (g.reps == 0) continue;
+    if (plan.tab.empty()) {
+      SubgConst& c0 = plan.c0.s;
+      c0.n = pc.s.n; c0.nd = pc.s.nd; c0.sqrt_n = pc.s.sqrt_n; c0.crit = pc.s.crit; c0.mix = pc.s.mix;
+      c0.sender_is_X = 1;
+      plan.c0.hrs = 1;
+    }
+    HrsPrivSegConst r;
+    std::memset(&r, 0, sizeof(r));
+    hrs_segment_record(pc, g, first, r);
+    r.bx = r.by = r.bs = r.lr = r.s_central = r.sn2x2 = r.crit_sqrt2_s = 0.0;   // per replicate
+    r.col_x = g.col_x; r.col_y = g.col_y;
+    r.log_inv_delta = log_inv_delta;
+    r.crit_sqrt2 = pc.s.crit * std::sqrt(2.0);
+    first += g.reps;
+    plan.tab.push_back(r);
+    plan.max_km = std::max(plan.max_km, pc.s.k * (int64_t)pc.s.m);
+  }
+  plan.lay = HrsPrivateLayout(plan.items, (int64_t)plan.tab.size(), t->n, t->p);
+  if (!plan.lay.ok)
+    return fail(DCOR_EINVAL, "%s: scratch bytes overflow (p = %lld, n = %lld)", entry, (long long)t->p,
+                (long long)t->n);
+  plan.lohi.resize(2 * (size_t)t->p);
+  for (int64_t c = 0; c < t->p; ++c) { plan.lohi[2 * (size_t)c] = t->lo[c]; plan.lohi[2 * (size_t)c + 1] = t->hi[c]; }
+  plan.pv.eps_mean = t->eps_mean; plan.pv.eps_m2 = t->eps_m2;
+  plan.pv.k0 = (uint32_t)t->seed_std; plan.pv.k1 = (uint32_t)(t->seed_std >> 32);
+  return DCOR_OK;
+}
+
 int64_t hrs_pair_count(const uint64_t* valid, int64_t n, int64_t col_x, int64_t col_y) {
   const int64_t nw = (n + 63) >> 6;
   const uint64_t* a = valid + col_x * nw;
@@ -710,8 +773,7 @@ void dcor_lambda_int_n(double n, double eta_s, double eta_r, double eps_s, doubl
 }
 
 double dcor_lambda_receiver_from_noise(double lam_s, double lam_o, double eps_s, double delta) {
-  const double b_s = 2.0 * lam_s / eps_s;  // real-data-sims.R:172
-  return (lam_s + b_s * std::log(1.0 / delta)) * lam_o;
+  return dcor::hrs_lambda_receiver(lam_s, lam_o, eps_s, std::log(1.0 / delta));  // real-data-sims.R:172
 }
 
 double dcor_qnorm(double p) {

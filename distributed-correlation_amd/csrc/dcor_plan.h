@@ -1,6 +1,6 @@
 // dcor_plan.h -- the host decisions that need no device: the error reporter, the argument checks,
 // every launch constant (R operation order, cited), the scratch layouts (dcor_layout.h) and the
-// segment planners of the eight segment-list entries, one plan struct each.  Plain C++: neither
+// segment planners of the nine segment-list entries, one plan struct each.  Plain C++: neither
 // this header nor dcor_plan.cpp includes the HIP runtime, so the unit compiles, runs and is
 // sanitized with a host compiler alone (tests/host/*.cpp over tests/host/check.h).  Not part of
 // the ABI.
@@ -106,7 +106,7 @@ struct HrsFusedSweepPlan {
 int plan_hrs_fused_sweep(const dcor_premat_subg* base, const dcor_panel* panel,
                          const dcor_hrs_segment* segs, int64_t nseg, HrsFusedSweepPlan& plan);
 
-// ---- the six table entries: int plan_X(desc, segs, nseg, XPlan&).  A planner resets its plan and
+// ---- the seven table entries: int plan_X(desc, segs, nseg, XPlan&).  A planner resets its plan and
 // makes every check of its entry after the null checks of the descriptor, segs and d_out, in the
 // order include/dcor.h documents; a segment without replicates is checked too.  On DCOR_OK the plan
 // is all the entry needs: tab, the records of the segments with reps > 0 in call order; items, the
@@ -137,6 +137,21 @@ struct HrsTablePlan : TablePlan<HrsPairSegConst, HrsTableLayout> {
 };
 int plan_hrs_table(const dcor_hrs_table_desc* t, const dcor_hrs_pair_segment* segs, int64_t nseg,
                    HrsTablePlan& plan);
+
+// dcor_hrs_private_table_launch.  A record holds plan_hrs_table's fields that do not depend on a
+// clip bound (the geometry, m_over_k, sqrt_k, eps_r, the keys, the place) and zeros in those that do:
+// every replicate derives them on the device with hrs_lambda_consts from its own release, out of
+// log_inv_delta = log(1 / delta) and crit_sqrt2 = crit * sqrt(2.0), both computed here.  lohi: the p
+// intervals as (lo, hi) pairs, the block the entry uploads; pv: the budgets and the key of
+// DCOR_SITE_STD; c0: n, nd, sqrt_n, crit, mix, hrs of any segment's make_subg, else zero.
+struct HrsPrivatePlan : TablePlan<HrsPrivSegConst, HrsPrivateLayout> {
+  std::vector<double> lohi;
+  HrsPrivCall pv{};
+  PrematSubgConst c0{};
+  int64_t max_km = 0;
+};
+int plan_hrs_private(const dcor_hrs_private_desc* t, const dcor_hrs_pair_segment* segs, int64_t nseg,
+                     HrsPrivatePlan& plan);
 
 // dcor_hrs_table_pairwise_launch.  The rows present in both columns: popcount of the ANDed mask words
 // (column c's nw = ceil(n / 64) words at valid + c * nw), the last word's bits at i >= n masked off.

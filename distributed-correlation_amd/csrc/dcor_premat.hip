@@ -1363,11 +1363,11 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_priv_standardize(const double* v
   for (int64_t i = threadIdx.x; i < n; i += DCOR_BLOCK) out[i] = (rclip(v[i], L) - mu) / sd;
 }
 
-// dp_sd (real-data-sims.R:73-84): out = {mean, sd}.
-__global__ __launch_bounds__(DCOR_BLOCK) void k_dp_sd(const double* x, int64_t n, double lo,
-                                                      double hi, double s_mu, double s_m2,
-                                                      const double* lap2, double* out) {
-  __shared__ double red[16 * DCOR_WAVES];
+// dp_sd's two means (real-data-sims.R:75-79) of one vector over a workgroup of DCOR_BLOCK threads:
+// mean(xc) and mean(xc^2) of xc = pmin(pmax(x, lo), hi), in every thread.  k_dp_sd and
+// k_hrs_private_prep share it, so a column's means carry the same bits in both.
+__device__ __forceinline__ void dp_clip_means(const double* __restrict__ x, int64_t n, double lo, double hi,
+                                              double* red, double* m1, double* m2) {
   DD a[2] = {{0, 0}, {0, 0}};
   for (int64_t i = threadIdx.x; i < n; i += DCOR_BLOCK) {
     const double xc = rclip_lohi(x[i], lo, hi);
@@ -1376,9 +1376,20 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_dp_sd(const double* x, int64_t n
   }
   block_sum_dd<2>(a, red);
   const double nd = (double)n;
-  const DD m1 = dd_div_d(a[0], nd), m2 = dd_div_d(a[1], nd);
-  const double mu = (m1.hi + m1.lo) + s_mu * lap2[0];
-  const double m2p = (m2.hi + m2.lo) + s_m2 * lap2[1];
+  const DD d1 = dd_div_d(a[0], nd), d2 = dd_div_d(a[1], nd);
+  *m1 = d1.hi + d1.lo;
+  *m2 = d2.hi + d2.lo;
+}
+
+// dp_sd (real-data-sims.R:73-84): out = {mean, sd}.
+__global__ __launch_bounds__(DCOR_BLOCK) void k_dp_sd(const double* x, int64_t n, double lo,
+                                                      double hi, double s_mu, double s_m2,
+                                                      const double* lap2, double* out) {
+  __shared__ double red[16 * DCOR_WAVES];
+  double m1, m2;
+  dp_clip_means(x, n, lo, hi, red, &m1, &m2);
+  const double mu = m1 + s_mu * lap2[0];
+  const double m2p = m2 + s_m2 * lap2[1];
   if (threadIdx.x == 0) {
     out[0] = mu;
     out[1] = sqrt(rmax(m2p - mu * mu, 0.0));
@@ -2180,6 +2191,194 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_table(PrematSubgConst p, i
   }
 }
 
+// ------------- the same on raw columns, the private standardisation drawn per replicate ---
+// dcor_hrs_private_table_launch: the replicate of k_hrs_table on the table standardize_dp would form
+// from this replicate's own dp_sd release of each column.  The standardised sample is an affine map
+// of the clipped raw one, z = (xc - mean) / den, with two scalars per column and replicate, so the
+// clipped raw columns are prepared once and the map is applied at gather time; the clip at +-lam of
+// k_hrs_table_prep is the identity on these values (subtraction and division by den > 0 are monotone
+// and lam is the larger end of the mapped interval) and is not applied.
+
+// One workgroup of DCOR_BLOCK threads per column c of D: k_dp_sd's means of the column clipped to
+// [lohi[2 c], lohi[2 c + 1]] (dp_clip_means: dcor_dp_sd's bits) to m12[2 c], m12[2 c + 1], then the
+// clipped column to cols + c npad with k_hrs_table_prep's layout and access widths.
+__global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_private_prep(const double* __restrict__ D, int64_t ld,
+                                                                 int64_t n, int64_t npad,
+                                                                 const double* __restrict__ lohi,
+                                                                 double* __restrict__ m12,
+                                                                 double* __restrict__ cols) {
+  __shared__ double red[16 * DCOR_WAVES];
+  const int64_t c = blockIdx.x;
+  const double* __restrict__ src = D + c * ld;
+  double2* __restrict__ dst = reinterpret_cast<double2*>(cols + c * npad);
+  const double lo = lohi[2 * c], hi = lohi[2 * c + 1];
+  double m1, m2;
+  dp_clip_means(src, n, lo, hi, red, &m1, &m2);
+  if (threadIdx.x == 0) { m12[2 * c] = m1; m12[2 * c + 1] = m2; }
+  const bool al16 = ((uintptr_t)src & 15) == 0;
+  for (int64_t j = threadIdx.x; 2 * j < npad; j += DCOR_BLOCK) {
+    const int64_t i = 2 * j;
+    double2 v = make_double2(0.0, 0.0);
+    if (i + 1 < n) {
+      if (al16) v = *reinterpret_cast<const double2*>(src + i);
+      else v = make_double2(src[i], src[i + 1]);
+      v = make_double2(rclip_lohi(v.x, lo, hi), rclip_lohi(v.y, lo, hi));
+    } else if (i < n) {
+      v.x = rclip_lohi(src[i], lo, hi);
+    }
+    dst[j] = v;
+  }
+}
+
+// HrsColumnLoad with the replicate's affine map applied at gather time: (xc - mean) / den per
+// column, a true division as in k_standardize_dp (a reciprocal multiply differs in the last bit).
+struct HrsAffineLoad {
+  const double* __restrict__ ca;
+  const double* __restrict__ cb;
+  double mean_a, den_a, mean_b, den_b;
+  __device__ __forceinline__ double2 map(double a, double b) const {
+    return make_double2((a - mean_a) / den_a, (b - mean_b) / den_b);
+  }
+  __device__ __forceinline__ double2 xy(uint32_t i) const { return map(ca[i], cb[i]); }
+  __device__ __forceinline__ double2 so(int64_t i) const { return map(ca[i], cb[i]); }
+  __device__ __forceinline__ void so2(int64_t b, double2& v0, double2& v1) const {
+    const double2 a = reinterpret_cast<const double2*>(ca)[b], y = reinterpret_cast<const double2*>(cb)[b];
+    v0 = map(a.x, y.x); v1 = map(a.y, y.y);
+  }
+};
+
+// A segment's fields that do not change with the replicate (hrs_seg_load's without the lambda-
+// dependent ones, which the table holds as zeros).
+__device__ __forceinline__ void hrs_private_seg_load(SegTab<HrsPrivSegConst> tab, int s, PrematSubgConst& p,
+                                                     HrsKeys& hk) {
+  SubgConst& c = p.s;
+  c.k = tab[s].k; c.m = tab[s].m; c.md_pow2 = tab[s].md_pow2;
+  c.md = tab[s].md; c.kd = tab[s].kd; c.inv_md = tab[s].inv_md;
+  c.m_over_k = tab[s].m_over_k; c.sqrt_k = tab[s].sqrt_k; c.eps_r = tab[s].eps_r;
+  hk.ni0 = tab[s].ni0; hk.ni1 = tab[s].ni1; hk.in0 = tab[s].in0; hk.in1 = tab[s].in1;
+  hk.rep_begin = tab[s].rep_begin;
+}
+
+// What a segment's pair brings to every one of its replicates: the columns' intervals and means and
+// the two host-computed factors of the constants.
+struct HrsPrivPair {
+  double lo_a, hi_a, m1_a, m2_a, lo_b, hi_b, m1_b, m2_b;
+  double log_inv_delta, crit_sqrt2;
+  uint32_t col_a, col_b;
+};
+__device__ __forceinline__ HrsPrivPair hrs_private_pair(SegTab<HrsPrivSegConst> tab, int s,
+                                                        const double* __restrict__ lohi,
+                                                        const double* __restrict__ m12) {
+  HrsPrivPair q;
+  q.col_a = (uint32_t)tab[s].col_x; q.col_b = (uint32_t)tab[s].col_y;
+  q.lo_a = lohi[2 * q.col_a]; q.hi_a = lohi[2 * q.col_a + 1];
+  q.lo_b = lohi[2 * q.col_b]; q.hi_b = lohi[2 * q.col_b + 1];
+  q.m1_a = m12[2 * q.col_a]; q.m2_a = m12[2 * q.col_a + 1];
+  q.m1_b = m12[2 * q.col_b]; q.m2_b = m12[2 * q.col_b + 1];
+  q.log_inv_delta = tab[s].log_inv_delta; q.crit_sqrt2 = tab[s].crit_sqrt2;
+  return q;
+}
+
+// A value every lane of the wave holds with the same bits, moved to scalar registers.
+__device__ __forceinline__ double wave_uniform(double x) {
+  const long long b = __double_as_longlong(x);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)b >> 32));
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+// Replicate `rep` of a pair: each column's release from its DCOR_SITE_STD block (column, rep) under
+// the call's key -- the block names no pair, eps or segment, so every pair that names a column sees
+// one release of it -- and from the two releases the lambda-dependent constants into p, with the
+// function the host check pins against plan_hrs_table (hrs_lambda_consts).  The streaming kernel and
+// the epilogue both call it.  The values are workgroup-uniform and every lane computes them
+// redundantly: two Philox blocks, four logs and some twenty divisions per lane and replicate, next to
+// one log and four divisions per sample of the replicate itself.  The alternative -- one wave computes,
+// the others read LDS -- has the same latency on the item's critical path and adds a barrier to every
+// item (it must also order the previous item's readers), so the redundant form is the simpler one
+// with nothing to synchronise; neither has been timed.  What the replicate's loops read (the map's
+// four scalars, bx, by, bs, lr) leaves through wave_uniform, so the loops hold them as k_hrs_table
+// holds its table constants, in scalar registers.
+__device__ __forceinline__ void hrs_private_item(const HrsPrivCall& pv, const HrsPrivPair& q, uint32_t rep,
+                                                 PrematSubgConst& p, HrsPriv& ra, HrsPriv& rb) {
+  SubgConst& c = p.s;
+  const U4 wa = draw(q.col_a, rep, DCOR_SITE_STD, pv.k0, pv.k1);
+  const U4 wb = draw(q.col_b, rep, DCOR_SITE_STD, pv.k0, pv.k1);
+  ra = hrs_private_release(q.m1_a, q.m2_a, q.lo_a, q.hi_a, c.nd, pv.eps_mean, pv.eps_m2,
+                           unit_laplace(u53(wa.w0, wa.w1)), unit_laplace(u53(wa.w2, wa.w3)));
+  rb = hrs_private_release(q.m1_b, q.m2_b, q.lo_b, q.hi_b, c.nd, pv.eps_mean, pv.eps_m2,
+                           unit_laplace(u53(wb.w0, wb.w1)), unit_laplace(u53(wb.w2, wb.w3)));
+  const HrsLamConst lc = hrs_lambda_consts(ra.lam, rb.lam, c.eps_r, c.md, c.nd, q.log_inv_delta, q.crit_sqrt2);
+  ra.mean = wave_uniform(ra.mean); ra.den = wave_uniform(ra.den);
+  rb.mean = wave_uniform(rb.mean); rb.den = wave_uniform(rb.den);
+  c.bx = wave_uniform(lc.bx); c.by = wave_uniform(lc.by); c.bs = wave_uniform(lc.bs); c.lr = wave_uniform(lc.lr);
+  c.s_central = lc.s_central; c.sn2x2 = lc.sn2x2; p.crit_sqrt2_s = lc.crit_sqrt2_s;
+}
+
+template <int WPE>
+__global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_private_table(PrematSubgConst p, HrsPrivCall pv, int pa,
+                                                                   int pc,
+                                                                   const HrsPrivSegConst* __restrict__ tab_g,
+                                                                   int nseg, int64_t items,
+                                                                   const double* __restrict__ lohi,
+                                                                   const double* __restrict__ m12,
+                                                                   const double* __restrict__ cols,
+                                                                   int64_t pitch,
+                                                                   SubgPartial* __restrict__ part) {
+  extern __shared__ double dsm[];
+  double* red = dsm;
+  uint16_t* gs = reinterpret_cast<uint16_t*>(dsm + 20 * DICT_NW);  // the largest k m of the segments
+  const SegTab<HrsPrivSegConst> tab = (SegTab<HrsPrivSegConst>)tab_g;
+  HrsKeys hk{0, 0, 0, 0, 0, pa, pc};
+  SegCursor cur;
+  int seg = 0, par = 0;
+  for (int64_t it = blockIdx.x; it < items; it += gridDim.x, par ^= 1) {
+    cur.seek(tab, nseg, items, it, [&](int s) {
+      hrs_private_seg_load(tab, s, p, hk);
+      seg = s;
+    });
+    const uint32_t rep = hk.rep_begin + (uint32_t)(it - cur.first);
+    // the pair's intervals and means are read again for every item (a dozen uniform loads) rather
+    // than held across the replicate's loops, which need the registers
+    const HrsPrivPair q = hrs_private_pair(tab, seg, lohi, m12);
+    HrsPriv ra, rb;
+    hrs_private_item(pv, q, rep, p, ra, rb);
+    const HrsAffineLoad ld{cols + (int64_t)q.col_a * pitch, cols + (int64_t)q.col_b * pitch, ra.mean, ra.den,
+                           rb.mean, rb.den};
+    hrs_fused_l2_item(p, hk, rep, ld, gs, red, par, part + it);
+  }
+}
+
+// k_hrs_sweep_fused_epilogue for that entry: the replicate's constants again, with the same
+// function (cheaper than carrying them: no scratch), then the shared epilogue item; the release
+// goes to priv when the caller asked for it.
+__global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_private_epilogue(PrematSubgConst p, HrsPrivCall pv,
+                                                                     const HrsPrivSegConst* __restrict__ tab_g,
+                                                                     int nseg, const double* __restrict__ lohi,
+                                                                     const double* __restrict__ m12,
+                                                                     const SubgPartial* __restrict__ part,
+                                                                     dcor_rep_out* out, double* __restrict__ priv) {
+  __shared__ SelScratch sel;
+  __shared__ double bc[2];
+  const SegTab<HrsPrivSegConst> tab = (SegTab<HrsPrivSegConst>)tab_g;
+  const int64_t r = blockIdx.x;
+  HrsKeys hk{0, 0, 0, 0, 0, 0, 0};   // the epilogue draws no permutation: pa, pc unused
+  const int s = __builtin_amdgcn_readfirstlane(seg_find(tab, nseg, r));
+  hrs_private_seg_load(tab, s, p, hk);
+  const HrsPrivPair q = hrs_private_pair(tab, s, lohi, m12);
+  const int64_t j = r - tab[s].first;
+  const int64_t row = tab[s].out_row + j;
+  const uint32_t rep = hk.rep_begin + (uint32_t)j;
+  HrsPriv ra, rb;
+  hrs_private_item(pv, q, rep, p, ra, rb);
+  if (priv != nullptr && threadIdx.x == 0) {
+    double* d = priv + 6 * row;
+    d[0] = ra.mean; d[1] = ra.sd; d[2] = ra.lam;
+    d[3] = rb.mean; d[4] = rb.sd; d[5] = rb.lam;
+  }
+  hrs_fused_epilogue_item(p, hk, rep, r, part, out + row, sel, bc);
+}
+
 // ------------------------- the same on the pairwise-complete cases of a table with gaps ---
 // dcor_hrs_table_pairwise_launch: a pair's samples are the rows present in both of its columns
 // (real-data-sims.R:119-120, 187-189), so n differs from pair to pair and the preparation is per
@@ -2411,6 +2610,29 @@ int launch_hrs_table(const PrematSubgConst& c, const double* D, int64_t p, int64
                      nseg, items, (const double*)cols, npad, (SubgPartial*)part);
   hipLaunchKernelGGL(k_hrs_sweep_fused_epilogue<HrsPairSegConst>, dim3((unsigned)items), dim3(DCOR_BLOCK), 0,
                      (hipStream_t)stream, c, tab, nseg, (const SubgPartial*)part, out);
+  return (int)hipGetLastError();
+}
+
+int launch_hrs_private_table(const PrematSubgConst& c, const HrsPrivCall& pv, const double* D, int64_t p,
+                             int64_t ld, const double* lohi, double* m12, double* cols, int64_t npad,
+                             const HrsPrivSegConst* tab, int nseg, int64_t items, int64_t max_km, void* part,
+                             dcor_rep_out* out, double* priv, void* stream) {
+  if (items <= 0 || nseg <= 0 || p <= 0) return 0;
+  int pa, pc;
+  hrs_feistel_split(c.s.n, &pa, &pc);
+  const int wsel = hrs_wpe();
+  const size_t lds = hrs_l2_lds_bytes(max_km);   // k_hrs_table's threads and LDS
+  typedef void (*PrivK)(PrematSubgConst, HrsPrivCall, int, int, const HrsPrivSegConst*, int, int64_t,
+                        const double*, const double*, const double*, int64_t, SubgPartial*);
+  const PrivK kern = wsel == 4 ? k_hrs_private_table<4> : k_hrs_private_table<6>;
+  int64_t grid = 0;
+  if (int e = persistent_grid((const void*)kern, DICT_NT, lds, items, &grid, kLdsDynMax)) return e;
+  hipLaunchKernelGGL(k_hrs_private_prep, dim3((unsigned)p), dim3(DCOR_BLOCK), 0, (hipStream_t)stream, D, ld,
+                     c.s.n, npad, lohi, m12, cols);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c, pv, pa, pc, tab,
+                     nseg, items, lohi, (const double*)m12, (const double*)cols, npad, (SubgPartial*)part);
+  hipLaunchKernelGGL(k_hrs_private_epilogue, dim3((unsigned)items), dim3(DCOR_BLOCK), 0, (hipStream_t)stream,
+                     c, pv, tab, nseg, lohi, (const double*)m12, (const SubgPartial*)part, out, priv);
   return (int)hipGetLastError();
 }
 

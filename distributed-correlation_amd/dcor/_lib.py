@@ -18,6 +18,7 @@ FAMILY_SIGN, FAMILY_SUBG = 0, 1
 DGP_GAUSSIAN, DGP_BERNOULLI, DGP_BOUNDED_FACTOR, DGP_MIX_GAUSSIAN = 0, 1, 2, 3
 MODE_AUTO, MODE_NORMAL, MODE_LAPLACE = 0, 1, 2
 SITE_DGP_A, SITE_DGP_B, SITE_FLIP, SITE_NI_LAP, SITE_SCALAR, SITE_MIX_Z, SITE_MIX_L, SITE_PERM = 1, 2, 3, 4, 5, 6, 7, 8
+SITE_STD = 17   # dcor_hrs_private_table_launch: column c's dp_sd draws, block c
 
 _MODES = {"auto": MODE_AUTO, "normal": MODE_NORMAL, "laplace": MODE_LAPLACE}
 
@@ -155,6 +156,14 @@ class HrsTableNaDesc(C.Structure):
                 ("nsim", C.c_int64)]
 
 
+class HrsPrivateDesc(C.Structure):
+    """dcor_hrs_private_desc (include/dcor.h): the shared table of RAW columns, their clip intervals
+    (HOST arrays of p doubles), the standardisation budgets and key, and the call-wide settings."""
+    _fields_ = [("n", C.c_int64), ("p", C.c_int64), ("ld", C.c_int64), ("D", _P), ("lo", _D), ("hi", _D),
+                ("eps_mean", C.c_double), ("eps_m2", C.c_double), ("seed_std", C.c_uint64),
+                ("alpha", C.c_double), ("delta", C.c_double), ("nsim", C.c_int64)]
+
+
 class SubgTableDesc(C.Structure):
     """dcor_subg_table_desc (include/dcor.h): the shared table (p columns of n samples, ld apart), its
     per-column sub-Gaussian parameters (a HOST array of p doubles) and the call-wide settings."""
@@ -231,6 +240,8 @@ SIGNATURES = {
                                         _P, _P]),
     "dcor_hrs_table_pairwise_launch": (C.c_int, [C.POINTER(HrsTableNaDesc), C.POINTER(HrsPairSegment),
                                                  C.c_int64, _P, _P]),
+    "dcor_hrs_private_table_launch": (C.c_int, [C.POINTER(HrsPrivateDesc), C.POINTER(HrsPairSegment),
+                                                C.c_int64, _P, _P, _P]),
     "dcor_subg_panel_launch": (C.c_int, [C.POINTER(SubgPanelDesc), C.POINTER(SubgSegment), C.c_int64,
                                          _P, _P]),
     "dcor_subg_table_launch": (C.c_int, [C.POINTER(SubgTableDesc), C.POINTER(SubgPairSegment), C.c_int64,

@@ -476,6 +476,82 @@ def corr_matrix_sweep(Z, lam, eps_grid=EPS_GRID, reps=R_PER_EPS, pairs=None, nsi
                                                           stream=stream), Z, eps_grid, reps, pairs)
 
 
+# ------------------- the same on raw columns, the private standardisation drawn per replicate
+STD_SEED = 433                                                   # the default key of the site-17 draws
+
+
+def _bounds(bounds, p):
+    b = np.asarray(bounds, dtype=np.float64)
+    if b.shape != (p, 2):
+        raise ValueError(f"bounds must hold one (lo, hi) pair per column ({p})")
+    return np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+
+
+def private_segments(raw, bounds, segs, eps_mean=EPS_MEAN, eps_m2=EPS_M2, seed_std=STD_SEED, nsim=2000,
+                     alpha=0.05, delta=None, return_priv=False, stream=None):
+    """table_segments on the RAW (n, p) table with the private standardisation of
+    real-data-sims.R:273-287 drawn anew in every replicate, in one native call
+    (dcor_hrs_private_table_launch): replicate r of a segment standardises column c with the dp_sd
+    release from the unit Laplace pair dcor_draws_launch(0, seed_std, 17, r, 1, 2 p)[2 c : 2 c + 2]
+    (budgets eps_mean, eps_m2 per column; bounds[c] = (lo, hi)) and runs the estimators on the result
+    under lam = lambda_from_priv of that release.  Its records equal table_segments(Z_r, lam_r, [the
+    segment at rep_begin = r, reps = 1]) byte for byte, (Z_r, lam_r) = standardize_table(raw, bounds,
+    lap = those draws); a column's release at r is the same for every pair and eps.  -> float64
+    [sum(reps), 6] in segment order, and with return_priv also [sum(reps), 6] (mean_x, sd_x, lam_x,
+    mean_y, sd_y, lam_y).  A NaN in raw raises: standardize_table(na="pairwise") +
+    corr_matrix_pairwise run tables with gaps."""
+    import ctypes as C
+
+    from . import _lib
+    from ._segcall import pack_segments, run_segment_call
+    from .signpanel import _table
+    segs = list(segs)
+    F, n, p = _table(raw)
+    if np.isnan(F).any():
+        raise ValueError("raw holds a NaN: a gap makes every record of its column's pairs NaN here; "
+                         "standardize_table(na=\"pairwise\") + corr_matrix_pairwise run a table with gaps")
+    lo, hi = _bounds(bounds, p)
+    for a, b, *_ in segs:
+        if not (0 <= int(a) < p and 0 <= int(b) < p):
+            raise ValueError(f"columns ({a}, {b}) outside [0, {p})")
+    arr, total = pack_segments(_lib.HrsPairSegment, segs, 6)
+    import torch
+    Dd = torch.as_tensor(F.reshape(-1, order="F"), device="cuda")   # the one upload
+    D = C.POINTER(C.c_double)
+    desc = _lib.HrsPrivateDesc(n=n, p=p, ld=n, D=Dd.data_ptr(), lo=lo.ctypes.data_as(D), hi=hi.ctypes.data_as(D),
+                               eps_mean=float(eps_mean), eps_m2=float(eps_m2), seed_std=int(seed_std),
+                               alpha=float(alpha), delta=1.0 / n if delta is None else float(delta),
+                               nsim=int(nsim))
+    if not return_priv:
+        launch = lambda d, a, k, out, sp: _lib.lib.dcor_hrs_private_table_launch(d, a, k, out, None, sp)
+        return run_segment_call(launch, desc, arr, len(segs), total, stream)
+    st = torch.cuda.current_stream() if stream is None else stream
+    with torch.cuda.stream(st):
+        priv = torch.empty((max(total, 1), 6), dtype=torch.float64, device="cuda")
+        launch = lambda d, a, k, out, sp: _lib.lib.dcor_hrs_private_table_launch(
+            d, a, k, out, C.c_void_p(priv.data_ptr()), sp)
+        res = run_segment_call(launch, desc, arr, len(segs), total, st)   # waits for the stream
+        return res, priv[:total].cpu().numpy()
+
+
+def corr_matrix_private(raw, bounds, eps, reps, pairs=None, eps_mean=EPS_MEAN, eps_m2=EPS_M2, seed_std=STD_SEED,
+                        nsim=2000, alpha=0.05, delta=None, stream=None):
+    """corr_matrix on the raw table with the standardisation drawn per replicate (private_segments):
+    the same pairs, keys and result; run r of every pair uses release r of its columns."""
+    run = lambda segs: private_segments(raw, bounds, segs, eps_mean=eps_mean, eps_m2=eps_m2, seed_std=seed_std,
+                                        nsim=nsim, alpha=alpha, delta=delta, stream=stream)
+    return _corr_matrix(run, raw, eps, reps, pairs)
+
+
+def corr_matrix_sweep_private(raw, bounds, eps_grid=EPS_GRID, reps=R_PER_EPS, pairs=None, eps_mean=EPS_MEAN,
+                              eps_m2=EPS_M2, seed_std=STD_SEED, nsim=2000, alpha=0.05, delta=None, stream=None):
+    """corr_matrix_sweep on the raw table with the standardisation drawn per replicate
+    (private_segments): the same pairs, keys and result."""
+    run = lambda segs: private_segments(raw, bounds, segs, eps_mean=eps_mean, eps_m2=eps_m2, seed_std=seed_std,
+                                        nsim=nsim, alpha=alpha, delta=delta, stream=stream)
+    return _corr_matrix_sweep(run, raw, eps_grid, reps, pairs)
+
+
 # ------------------------------- the same on pairwise-complete cases of a table with gaps
 def valid_mask(Z):
     """The presence masks of the (n, p) table Z as dcor_hrs_table_pairwise_launch takes them: uint64

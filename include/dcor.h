@@ -556,6 +556,59 @@ typedef struct dcor_hrs_table_na_desc {
 int dcor_hrs_table_pairwise_launch(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair_segment* segs,
                                    int64_t nseg, dcor_rep_out* d_out, void* stream);
 
+/* dcor_hrs_table_launch on RAW columns, with the private standardisation of the reference's real
+ * pipeline (dp_sd -> standardize_dp -> lambda_from_priv -> correlation_NI_subG / ci_INT_subG,
+ * real-data-sims.R:273-323) drawn anew in every replicate, so the replicates show the spread and the
+ * CI coverage of the whole mechanism and not of the estimators on one frozen draw of (mean, sd).  D
+ * holds p raw columns of n samples, column c at D + c * ld, clipped to [lo[c], hi[c]].
+ * Draw contract: in replicate r (a segment's rep_begin + j) column c takes two unit Laplace draws
+ * from Philox block (index = c, rep = r, DCOR_SITE_STD, 0) under key seed_std: words (0,1) the
+ * mean's, words (2,3) the second moment's -- dcor_draws_launch(0, seed_std, DCOR_SITE_STD, r, 1, 2 p)
+ * is [mean, m2] of column 0, of column 1, ..., the `lap` of the Python layer's standardize_table.  A
+ * column's release in replicate r depends on (column, lo, hi, eps_mean, eps_m2, seed_std, r) alone:
+ * never on the pair, the eps or the segment, as a server releases its standardisation once and every
+ * pair that names the column uses it.  With m1, m2 the compensated means of xc = clip(x, lo, hi) and
+ * of xc^2 (dcor_dp_sd's), per replicate and column, in this order:
+ *   mean = m1 + ((hi - lo) / (n eps_mean)) lap0,  m2p = m2 + ((hi^2 - lo^2) / (n eps_m2)) lap1,
+ *   sd = sqrt(max(m2p - mean mean, 0)),  den = max(sd, 1e-8),
+ *   lam = max(|(lo - mean) / den|, |(hi - mean) / den|),
+ * and the replicate's sample i of column c is (xc[i] - mean) / den, an IEEE division.
+ * Contract: the records of replicate r of a segment on (col_x, col_y) equal, byte for byte, the
+ * records of dcor_hrs_table_launch for that replicate alone (rep_begin = r, reps = 1; the same
+ * seeds, eps, alpha, delta, nsim) on the table whose column c is dcor_standardize_dp(D[c], lo[c],
+ * hi[c], mean_c, sd_c, 1e-8) with lam[c] = dcor_lambda_from_priv(lo[c], hi[c], mean_c, sd_c, 1e-8)
+ * and (mean_c, sd_c) = dcor_dp_sd(D[c], n, lo[c], hi[c], eps_mean, eps_m2, the two draws above).  The
+ * draw sites of the estimators, the HRS geometry and the Feistel split are dcor_hrs_table_launch's.
+ * Records depend only on (table, lo, hi, budgets, seeds, eps, replicate), never on the segment
+ * split, the segment order or out_row, so sharding by rep_begin over calls or GPUs stays exact.
+ * d_priv, when not null: record out_row + j also gets d_priv[6 (out_row + j) .. + 5] = (mean_x, sd_x,
+ * lam_x, mean_y, sd_y, lam_y), the bits the host helpers return.
+ * A NaN in column c makes that column's sums NaN, and so every record (and d_priv triple) of every
+ * pair that names c; other pairs are unaffected.  Gaps are dcor_hrs_table_pairwise_launch's job.
+ * Privacy accounting of one replicate: eps_mean + eps_m2 per column, plus eps per pair it joins.
+ * Checks, all on the host before anything is enqueued and before any device access (an invalid call
+ * returns its code and leaves d_out and d_priv untouched; dcor_last_error names the column or the
+ * segment): those of dcor_hrs_table_launch (2 <= n <= 65536) with lam replaced by non-null lo, hi,
+ * every lo[c], hi[c] finite with lo[c] < hi[c], and eps_mean, eps_m2 finite and > 0.  nseg == 0 or
+ * no replicates at all returns DCOR_OK with no device work.  Asynchronous on `stream`, no host
+ * synchronisation; scratch is stream-ordered (8 B per sample and column, 16 B per column for m1, m2,
+ * 16 B per column for lo, hi, the segment table, 80 B per replicate) -- no noise array, no
+ * standardised table in memory, no dcor_panel.  D, lo, hi and segs are borrowed for the call only (D
+ * until the call's work on `stream` has run). */
+typedef struct dcor_hrs_private_desc {
+  int64_t n, p, ld;         /* as dcor_hrs_table_desc: RAW columns, column c = D + c * ld (DEVICE) */
+  const double* D;
+  const double* lo;         /* HOST, [p]: raw clip interval of column c, finite, lo[c] < hi[c] */
+  const double* hi;
+  double eps_mean, eps_m2;  /* > 0, finite: dp_sd's eps1, eps2 (real-data-sims.R:73-84) */
+  uint64_t seed_std;        /* Philox key of the standardisation draws, call-wide */
+  double alpha, delta;      /* as dcor_hrs_table_desc */
+  int64_t nsim;
+} dcor_hrs_private_desc;
+int dcor_hrs_private_table_launch(const dcor_hrs_private_desc* t, const dcor_hrs_pair_segment* segs,
+                                  int64_t nseg, dcor_rep_out* d_out, double* d_priv /* nullable */,
+                                  void* stream);
+
 /* The sub-Gaussian estimators of the simulation (correlation_NI_subG + ci_INT_subG,
  * ver-cor-subG.R:25-108: contiguous batches, lambda_n / lambda_INT_n, any (eps1, eps2), either
  * sender) on the caller's own (X, Y), prepared once and shared by every replicate, with every noise
@@ -771,7 +824,10 @@ enum {
   DCOR_SITE_MIX_L = 7,   /* mixquant unit Laplace, 2 per block                    */
   DCOR_SITE_PERM = 8,    /* HRS random-batch permutation keys (dcor_perm_launch)  */
   DCOR_SITE_ZIG = 9,     /* Gaussian DGP ziggurat retries (counter word 3 = 2 attempt + which) */
-  DCOR_SITE_ZIG_TAIL = 10 /* Gaussian DGP ziggurat tail (counter word 3 = 2 step + which) */
+  DCOR_SITE_ZIG_TAIL = 10, /* Gaussian DGP ziggurat tail (counter word 3 = 2 step + which) */
+  /* 11 .. 16: the HRS estimators' sites (NI Laplace X / Y, INT local / central, mixquant Z / L) */
+  DCOR_SITE_STD = 17     /* dcor_hrs_private_table_launch, block c: column c's dp_sd unit Laplace,
+                            mean (w0,w1), second moment (w2,w3), under key seed_std */
 };
 
 #ifdef __cplusplus
