@@ -750,6 +750,78 @@ def hrs_table_na(R, p=4, gap=0.2, repeats=5):
     print(json.dumps({"config": "HTN-check", "full_mask_records_bit_equal": same}), flush=True)
 
 
+def hrs_private_na(R, p=4, gap=0.2, repeats=5):
+    """HTPN: HTN's stand-in table, masks and segment list with raw columns and bounds as in HTP (column c
+    is 60 + 10 z_c, clipped to [30, 90]): the private standardisation drawn per replicate and every
+    pair on its own n_ab rows, in one dcor_hrs_private_pairwise_launch call.  Beside it the same entry
+    on the complete table (HTPN-full), dcor_hrs_private_table_launch on that table (HTPN-full-private:
+    the same work per sample without the pack, records bit-equal), and what a user had to do before the
+    entry (HTPN-hostloop): per replicate number one draws launch, p dp_sd / standardize_dp round trips
+    and one dcor_hrs_table_pairwise_launch call of single-replicate segments -- timed once, the records
+    bit-equal to HTPN's.  The other lines: the median and the least of `repeats` timed calls after one
+    warm-up.  Not in the default list: reach it with --only HTPN."""
+    import ctypes as C
+
+    import numpy as np
+    import torch
+    from dcor import _lib, api, hrs, signpanel
+    n = 19433
+    raw = np.asfortranarray(60.0 + 10.0 * signpanel.standin_table(n, p, 0.3))
+    bounds = [(30.0, 90.0)] * p
+    pairs = signpanel.all_pairs(p)
+    ne = len(hrs.EPS_GRID)
+    V = np.random.default_rng(11).random((n, p)) >= gap
+    rawna = np.asfortranarray(np.where(V, raw, np.nan))
+    valid, full = hrs.valid_mask(rawna), hrs.valid_mask(raw)
+    segs = [(a, b, e, 10 + 1000 * (j * ne + idx), 20 + 1000 * (j * ne + idx), 0, R)
+            for j, (a, b) in enumerate(pairs) for idx, e in enumerate(hrs.EPS_GRID, start=1)]
+    n_pair = [int((V[:, a] & V[:, b]).sum()) for a, b in pairs]
+    total = len(segs) * R
+
+    def host_loop():
+        out = np.empty((len(segs), R, 6))
+        lap = torch.empty(2 * p, dtype=torch.float64, device="cuda")
+        sp = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        for r in range(R):
+            _lib.check(_lib.lib.dcor_draws_launch(0, hrs.STD_SEED, _lib.SITE_STD, r, 1, 2 * p,
+                                                  C.c_void_p(lap.data_ptr()), sp))
+            t = hrs.standardize_table(rawna, bounds, lap=lap.cpu().numpy(), na="pairwise")
+            one = [(a, b, e, sn, si, r, 1) for a, b, e, sn, si, _, _ in segs]
+            out[:, r] = hrs.pairwise_segments(t["Z"], t["lam"], one, valid=valid)
+        return out.reshape(total, 6)
+
+    pk = "k_hrs_col_compact + k_hrs_col_means + k_hrs_pair_pack + k_hrs_private_pair_table + k_hrs_private_epilogue"
+    res = {}
+    for name, fn, rows, kernel, reps in (
+            ("HTPN", lambda: hrs.private_pairwise_segments(rawna, bounds, segs, valid=valid), n_pair, pk, repeats),
+            ("HTPN-full", lambda: hrs.private_pairwise_segments(raw, bounds, segs, valid=full), [n] * len(pairs), pk,
+             repeats),
+            ("HTPN-full-private", lambda: hrs.private_segments(raw, bounds, segs, delta=1.0 / n), [n] * len(pairs),
+             "k_hrs_private_prep + k_hrs_private_table + k_hrs_private_epilogue", repeats),
+            ("HTPN-hostloop", host_loop, n_pair, "k_draws, k_dp_sd, k_standardize_dp and HTN's, per replicate number",
+             1)):
+        if reps > 1:
+            fn()    # warm-up
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            res[name] = fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        t = float(np.median(ts))
+        samples = sum(rows) * ne * R     # samples every replicate of the call reads
+        line(name, n=n, p=p, pairs=len(pairs), rows_per_pair=rows, replicates=total, seconds=t,
+             seconds_min=min(ts), reps_per_s=total / t, sample_reps_per_s=samples / t,
+             finite=bool(np.isfinite(res[name]).all()), kernel=kernel,
+             note="host wall time, uploads and the copy back of the records included")
+    bits = {k: v.view(np.uint64) for k, v in res.items()}
+    print(json.dumps({"config": "HTPN-check",
+                      "hostloop_records_bit_equal": bool(np.array_equal(bits["HTPN"], bits["HTPN-hostloop"])),
+                      "full_mask_records_bit_equal": bool(np.array_equal(bits["HTPN-full"],
+                                                                         bits["HTPN-full-private"]))}), flush=True)
+
+
 def subg():
     from dcor.sim import CellSpec, simulate
     cell = CellSpec(n=100_000, rho=0.5, eps1=1.0, eps2=1.0, family="subG", dgp="bounded_factor", seed=5)
@@ -1069,6 +1141,7 @@ def main():
     if "HT-pairs" in which: hrs_table(a.hs_R, arm="pairs")
     if "HTN" in which: hrs_table_na(a.hs_R)
     if "HTP" in which: hrs_private(a.hs_R)
+    if "HTPN" in which: hrs_private_na(a.hs_R)
     if "S" in which: subg()
     if "R1" in which: rstream_c1()
     if "RG" in which: rstream_grid()

@@ -1079,7 +1079,7 @@ static int seg_args(const char* entry, const void* desc, const void* segs, int64
   return DCOR_OK;
 }
 
-// The seven table entries: the argument check, the planner, the device, one launch over the plan.
+// The eight table entries: the argument check, the planner, the device, one launch over the plan.
 int dcor_sign_panel_launch(const dcor_sign_panel_desc* p, const dcor_sign_segment* segs,
                            int64_t nseg, dcor_rep_out* d_out, void* stream) {
   if (int st = seg_args("sign_panel", p, segs, nseg, d_out)) return st;
@@ -1157,6 +1157,26 @@ int dcor_hrs_private_table_launch(const dcor_hrs_private_desc* t, const dcor_hrs
                                     lay.cols(buf), lay.npad, lay.tab(buf), (int)plan.tab.size(), plan.items,
                                     plan.max_km, buf, d_out, d_priv, stream);
   }, false, {{lay.lohi_off, plan.lohi.data(), plan.lohi.size() * sizeof(double)}});
+}
+
+int dcor_hrs_private_pairwise_launch(const dcor_hrs_private_na_desc* t, const dcor_hrs_pair_segment* segs,
+                                     int64_t nseg, dcor_rep_out* d_out, double* d_priv, void* stream) {
+  if (int st = seg_args("hrs_private_pairwise", t, segs, nseg, d_out)) return st;
+  if (nseg == 0) return DCOR_OK;
+  HrsPrivPairPlan plan;
+  if (int st = plan_hrs_private_pairwise(t, segs, nseg, plan)) return st;
+  if (plan.items == 0) return DCOR_OK;
+  if (int st = need_device()) return st;
+  const HrsPrivPairLayout& lay = plan.lay;
+  return with_table("hrs_private_pairwise", lay.bytes, plan.tab, lay.tab_off, stream, [&](void* buf) {
+    return launch_hrs_private_pair_table(plan.c0, plan.pv, t->D, t->p, t->n, t->ld, lay.lohi(buf), lay.masks(buf),
+                                         lay.nw, lay.cols(buf), lay.comp(buf), lay.m12(buf), lay.slots(buf),
+                                         (int)plan.slots.size(), lay.panels(buf), lay.tab(buf),
+                                         (int)plan.tab.size(), plan.items, plan.max_km, buf, d_out, d_priv, stream);
+  }, false, {{lay.slot_off, plan.slots.data(), plan.slots.size() * sizeof(HrsPairSlot)},
+             {lay.col_off, plan.cols.data(), plan.cols.size() * sizeof(HrsPrivCol)},
+             {lay.lohi_off, plan.lohi.data(), plan.lohi.size() * sizeof(double)},
+             {lay.mask_off, t->valid, (size_t)t->p * (size_t)lay.nw * sizeof(uint64_t)}});
 }
 
 int dcor_subg_panel_launch(const dcor_subg_panel_desc* p, const dcor_subg_segment* segs,

@@ -449,6 +449,43 @@ int launch_hrs_private_table(const PrematSubgConst& c, const HrsPrivCall& pv, co
                              const HrsPrivSegConst* tab, int nseg, int64_t items, int64_t max_km, void* part,
                              dcor_rep_out* out, double* priv, void* stream);
 
+// ---- the private standardisation per replicate on the pairwise-complete cases of a table with gaps
+// (dcor_hrs_private_pairwise_launch) ----
+// The private entry's record with what HrsPairNaSegConst adds (the pair's own n = n_ab, nd, sqrt_n,
+// the Feistel split and the panel) and the two columns' own counts: dp_sd drops a column's own NA
+// (real-data-sims.R:74), so a column's release divides by n_c = popcount(valid[c]) -- n_x, n_y, as
+// doubles -- while the geometry, delta = 1 / n_ab and hrs_lambda_consts take the pair's n_ab (:119-120,
+// :187-189).  log_inv_delta is the pair's: log(1 / delta) of the descriptor's delta, or of 1 / n_ab.
+struct HrsPrivNaSegConst : HrsPrivSegConst {
+  int64_t n;
+  double nd, sqrt_n;
+  int32_t pa, pc;
+  int64_t panel;
+  double n_x, n_y;
+};
+static_assert(sizeof(HrsPrivNaSegConst) == 240, "the private pairwise entry's device table stride");
+// A column of that call: its present rows and the first element of its compacted copy (doubles from
+// the first column's; each copy starts 256-B aligned).
+struct HrsPrivCol {
+  int64_t n_c, off;
+};
+static_assert(sizeof(HrsPrivCol) == 16, "the private pairwise entry's column table stride");
+// doubles a column's compacted copy takes
+inline int64_t hrs_priv_col_elems(int64_t n_c) { return (n_c + 31) & ~(int64_t)31; }
+// The preparation launches -- one workgroup per column: its present rows compacted in row order to
+// comp + cols[c].off (k_hrs_pair_pack's ranks under one mask), then k_dp_sd's means of that copy
+// clipped to [lohi[2 c], lohi[2 c + 1]] to m12[2 c], m12[2 c + 1] (dcor_dp_sd's bits on the column
+// without its gaps); one workgroup per slot: k_hrs_pair_pack with the clip to the raw interval in
+// place of the clip at +-lam -- then the streaming and epilogue launches over `items` replicates of
+// the nseg >= 1 segments in `tab` (device), as launch_hrs_pair_table and launch_hrs_private_table.
+// c: crit, mix, hrs.  lohi, masks (p x nw words), cols, slots: device.  priv: as above.
+int launch_hrs_private_pair_table(const PrematSubgConst& c, const HrsPrivCall& pv, const double* D, int64_t p,
+                                  int64_t n, int64_t ld, const double* lohi, const uint64_t* masks, int64_t nw,
+                                  const HrsPrivCol* cols, double* comp, double* m12, const HrsPairSlot* slots,
+                                  int nslot, double2* panels, const HrsPrivNaSegConst* tab, int nseg,
+                                  int64_t items, int64_t max_km, void* part, dcor_rep_out* out, double* priv,
+                                  void* stream);
+
 // ---- sub-G simulation estimators on a shared panel (dcor_subg_panel_launch; dcor_subgpanel.hip) ----
 // One segment of a sub-G panel call: the part of SubgConst that depends on the segment's (eps1,
 // eps2) (make_subg's values, unchanged; ls follows the sender's eta), its Philox key and its place

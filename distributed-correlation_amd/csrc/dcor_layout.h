@@ -176,6 +176,39 @@ struct HrsPairTableLayout : Carver {
   double2* panels(void* base) const { return (double2*)((char*)base + panel_off); }
 };
 
+// Private pairwise HRS-table scratch: partials (one SubgPartial per replicate of the call) | the
+// segment table, the slot table, the column table | the p clip intervals (lo, hi) | the p pairs
+// (m1, m2) the preparation writes | the p masks of nw = ceil(n / 64) words | the columns' compacted
+// copies (comp_elems doubles in all: 8 B per present row) | the slots' packed panels (panel_elems
+// double2 in all).
+struct HrsPrivPairLayout : Carver {
+  int64_t nw = 0;
+  size_t tab_off = 0, slot_off = 0, col_off = 0, lohi_off = 0, m12_off = 0, mask_off = 0, comp_off = 0,
+         panel_off = 0;
+  HrsPrivPairLayout(int64_t items = 0, int64_t nseg = 0, int64_t nslot = 0, int64_t n = 0, int64_t p = 0,
+                    int64_t comp_elems = 0, int64_t panel_elems = 0)
+      : Carver(n >= 1 && p >= 1), nw((n + 63) >> 6) {
+    add(items, sizeof(SubgPartial));
+    tab_off = add(nseg, sizeof(HrsPrivNaSegConst));
+    slot_off = add(nslot, sizeof(HrsPairSlot));
+    col_off = add(p, sizeof(HrsPrivCol));
+    lohi_off = add(p, 2 * sizeof(double));
+    m12_off = add(p, 2 * sizeof(double));
+    mask_off = add({p, nw}, sizeof(uint64_t));
+    comp_off = add(comp_elems, sizeof(double));
+    panel_off = add(panel_elems, sizeof(double2));
+  }
+  static HrsPrivPairLayout columns(int64_t n, int64_t p) { return HrsPrivPairLayout(0, 0, 0, n, p, 0, 0); }
+  HrsPrivNaSegConst* tab(void* base) const { return (HrsPrivNaSegConst*)((char*)base + tab_off); }
+  HrsPairSlot* slots(void* base) const { return (HrsPairSlot*)((char*)base + slot_off); }
+  HrsPrivCol* cols(void* base) const { return (HrsPrivCol*)((char*)base + col_off); }
+  double* lohi(void* base) const { return (double*)((char*)base + lohi_off); }
+  double* m12(void* base) const { return (double*)((char*)base + m12_off); }
+  uint64_t* masks(void* base) const { return (uint64_t*)((char*)base + mask_off); }
+  double* comp(void* base) const { return (double*)((char*)base + comp_off); }
+  double2* panels(void* base) const { return (double2*)((char*)base + panel_off); }
+};
+
 // Sub-G panel scratch: the segment table | the slot table | the batch means of every slot (16 B
 // per batch) | the packed panel (x, y) of n rounded up to npad (a multiple of 4; zeros from n on).
 // nmeans: the sum of the slots' k.

@@ -1,6 +1,6 @@
 // dcor_plan.cpp -- the device-free half of the host side (dcor_plan.h): the error reporter, the
 // argument checks of the reference's stopifnot() calls, every data-independent scalar of the
-// estimators (R operation order, cited), and the segment planners of the nine segment-list
+// estimators (R operation order, cited), and the segment planners of the ten segment-list
 // entries.  No HIP: this file and the headers it includes compile with a host compiler alone.
 #include "dcor_plan.h"
 
@@ -373,6 +373,89 @@ int check_alpha_nsim(int64_t n, double alpha, int64_t nsim) {
   return make_mix(nsim, alpha, mx);
 }
 
+// The standardisation's part of the two private descriptors (T: dcor_hrs_private_desc or
+// dcor_hrs_private_na_desc), in the entries' order: D's alignment, every interval, the budgets.
+template <class T> int private_release_args(const char* entry, const T& t) {
+  if ((uintptr_t)t.D & 7) return fail(DCOR_EINVAL, "%s: D must be aligned to 8 bytes", entry);
+  for (int64_t c = 0; c < t.p; ++c)
+    if (!std::isfinite(t.lo[c]) || !std::isfinite(t.hi[c]) || !(t.lo[c] < t.hi[c]))
+      return fail(DCOR_EINVAL, "%s: column %lld: need finite lo < hi (got %g, %g)", entry, (long long)c,
+                  t.lo[c], t.hi[c]);
+  if (!std::isfinite(t.eps_mean) || !std::isfinite(t.eps_m2) || !(t.eps_mean > 0.0) || !(t.eps_m2 > 0.0))
+    return fail(DCOR_EINVAL, "%s: eps_mean, eps_m2 must be finite and > 0 (got %g, %g)", entry, t.eps_mean,
+                t.eps_m2);
+  return DCOR_OK;
+}
+// What the two private plans carry of their descriptor: the intervals as (lo, hi) pairs, the budgets
+// and the key of DCOR_SITE_STD.
+template <class T> void private_release_plan(const T& t, std::vector<double>& lohi, HrsPrivCall& pv) {
+  lohi.resize(2 * (size_t)t.p);
+  for (int64_t c = 0; c < t.p; ++c) { lohi[2 * (size_t)c] = t.lo[c]; lohi[2 * (size_t)c + 1] = t.hi[c]; }
+  pv.eps_mean = t.eps_mean; pv.eps_m2 = t.eps_m2;
+  pv.k0 = (uint32_t)t.seed_std; pv.k1 = (uint32_t)(t.seed_std >> 32);
+}
+// A private segment's constants and record at sample count n and clip delta: make_subg's checks and
+// everything of it that no clip bound enters (the bounds are placeholders), the lambda-dependent
+// fields zero (every replicate derives its own), the two host factors of that derivation.
+int private_segment_record(int64_t n, double delta, double alpha, int64_t nsim, const dcor_hrs_pair_segment& g,
+                           int64_t first, PrematSubgConst& pc, HrsPrivSegConst& r) {
+  std::memset(&pc, 0, sizeof(pc));
+  if (int st = make_subg(n, g.eps, g.eps, 1.0, 1.0, alpha, 1, 1.0, 1.0, 1.0, 1.0, 1.0, delta, nsim, pc.s, &pc.lo_,
+                         &pc.crit_sqrt2_s))
+    return st;
+  hrs_segment_record(pc, g, first, r);
+  r.bx = r.by = r.bs = r.lr = r.s_central = r.sn2x2 = r.crit_sqrt2_s = 0.0;   // per replicate
+  r.col_x = g.col_x; r.col_y = g.col_y;
+  r.log_inv_delta = std::log(1.0 / delta);   // lambda_receiver_from_noise's, rds:172
+  r.crit_sqrt2 = pc.s.crit * std::sqrt(2.0);
+  return DCOR_OK;
+}
+// The call-wide constants of a private call from any segment's (n, nd, sqrt_n: the pairwise entry's
+// records carry their own).
+void private_call_consts(const PrematSubgConst& pc, PrematSubgConst& c0) {
+  c0.s.n = pc.s.n; c0.s.nd = pc.s.nd; c0.s.sqrt_n = pc.s.sqrt_n; c0.s.crit = pc.s.crit; c0.s.mix = pc.s.mix;
+  c0.s.sender_is_X = 1;
+  c0.hrs = 1;
+}
+
+// The pairs of a pairwise call: every segment's n_ab (a pair is counted once), and the distinct
+// ordered pairs of the segments with replicates as slots in order of first use, each panel behind the
+// one before.
+struct PairSlots {
+  struct Pair { int64_t n_ab, slot; };   // slot: -1 until a segment with replicates names the pair
+  std::map<std::pair<int32_t, int32_t>, Pair> seen;
+  Pair& pair(const uint64_t* valid, int64_t n, const dcor_hrs_pair_segment& g) {
+    const auto at = seen.emplace(std::make_pair(g.col_x, g.col_y), Pair{0, -1});
+    if (at.second) at.first->second.n_ab = hrs_pair_count(valid, n, g.col_x, g.col_y);
+    return at.first->second;
+  }
+  // segment i's pair, refused unless 2 <= n_ab <= DCOR_DICT_NMAX
+  int checked(const char* entry, const uint64_t* valid, int64_t n, const dcor_hrs_pair_segment& g, int64_t i,
+              Pair** out) {
+    Pair& pr = pair(valid, n, g);
+    *out = &pr;
+    if (pr.n_ab < 2 || pr.n_ab > DCOR_DICT_NMAX)
+      return fail(DCOR_EINVAL, "%s: segment %lld: columns (%d, %d) have n_ab = %lld pairwise-complete rows, "
+                  "must be in [2, %d]: a replicate keeps u16 indices of the compacted rows in LDS", entry,
+                  (long long)i, (int)g.col_x, (int)g.col_y, (long long)pr.n_ab, DCOR_DICT_NMAX);
+    return DCOR_OK;
+  }
+  // the pair's slot, a new one when no segment has run the pair before
+  const HrsPairSlot& slot(Pair& pr, const dcor_hrs_pair_segment& g, std::vector<HrsPairSlot>& slots,
+                          int64_t& panel_elems) {
+    if (pr.slot < 0) {
+      HrsPairSlot sl;
+      std::memset(&sl, 0, sizeof(sl));
+      sl.n_ab = pr.n_ab; sl.panel = panel_elems;
+      sl.col_x = g.col_x; sl.col_y = g.col_y;
+      panel_elems += hrs_pair_panel_elems(pr.n_ab);
+      pr.slot = (int64_t)slots.size();
+      slots.push_back(sl);
+    }
+    return slots[(size_t)pr.slot];
+  }
+};
+
 }  // namespace
 
 dcor_premat_subg hrs_segment_desc(const dcor_premat_subg& base, const dcor_hrs_segment& g) {
@@ -537,41 +620,19 @@ int plan_hrs_private(const dcor_hrs_private_desc* t, const dcor_hrs_pair_segment
   if (!HrsPrivateLayout::columns(t->n, t->p).ok)
     return fail(DCOR_EINVAL, "%s: p * npad * 8 scratch bytes overflow (p = %lld, n = %lld)", entry,
                 (long long)t->p, (long long)t->n);
-  if ((uintptr_t)t->D & 7) return fail(DCOR_EINVAL, "%s: D must be aligned to 8 bytes", entry);
-  for (int64_t c = 0; c < t->p; ++c)
-    if (!std::isfinite(t->lo[c]) || !std::isfinite(t->hi[c]) || !(t->lo[c] < t->hi[c]))
-      return fail(DCOR_EINVAL, "%s: column %lld: need finite lo < hi (got %g, %g)", entry, (long long)c,
-                  t->lo[c], t->hi[c]);
-  if (!std::isfinite(t->eps_mean) || !std::isfinite(t->eps_m2) || !(t->eps_mean > 0.0) || !(t->eps_m2 > 0.0))
-    return fail(DCOR_EINVAL, "%s: eps_mean, eps_m2 must be finite and > 0 (got %g, %g)", entry, t->eps_mean,
-                t->eps_m2);
+  if (int st = private_release_args(entry, *t)) return st;
   if (!(t->delta > 0.0)) return fail(DCOR_EINVAL, "%s: delta must be positive", entry);
   if (int st = check_alpha_nsim(t->n, t->alpha, t->nsim)) return st;
   if (int st = segment_heads(entry, segs, nseg, t->p, &plan.items)) return st;
-  const double log_inv_delta = std::log(1.0 / t->delta);   // lambda_receiver_from_noise's, rds:172
   int64_t first = 0;
   for (int64_t i = 0; i < nseg; ++i) {
     const dcor_hrs_pair_segment& g = segs[i];
-    // make_subg's checks and everything of it that no clip bound enters; the bounds are placeholders
     PrematSubgConst pc;
-    std::memset(&pc, 0, sizeof(pc));
-    if (int st = make_subg(t->n, g.eps, g.eps, 1.0, 1.0, t->alpha, 1, 1.0, 1.0, 1.0, 1.0, 1.0, t->delta,
-                           t->nsim, pc.s, &pc.lo_, &pc.crit_sqrt2_s))
-      return st;
-    if (g.reps == 0) continue;
-    if (plan.tab.empty()) {
-      SubgConst& c0 = plan.c0.s;
-      c0.n = pc.s.n; c0.nd = pc.s.nd; c0.sqrt_n = pc.s.sqrt_n; c0.crit = pc.s.crit; c0.mix = pc.s.mix;
-      c0.sender_is_X = 1;
-      plan.c0.hrs = 1;
-    }
     HrsPrivSegConst r;
     std::memset(&r, 0, sizeof(r));
-    hrs_segment_record(pc, g, first, r);
-    r.bx = r.by = r.bs = r.lr = r.s_central = r.sn2x2 = r.crit_sqrt2_s = 0.0;   // per replicate
-    r.col_x = g.col_x; r.col_y = g.col_y;
-    r.log_inv_delta = log_inv_delta;
-    r.crit_sqrt2 = pc.s.crit * std::sqrt(2.0);
+    if (int st = private_segment_record(t->n, t->delta, t->alpha, t->nsim, g, first, pc, r)) return st;
+    if (g.reps == 0) continue;
+    if (plan.tab.empty()) private_call_consts(pc, plan.c0);
     first += g.reps;
     plan.tab.push_back(r);
     plan.max_km = std::max(plan.max_km, pc.s.k * (int64_t)pc.s.m);
@@ -580,10 +641,7 @@ int plan_hrs_private(const dcor_hrs_private_desc* t, const dcor_hrs_pair_segment
   if (!plan.lay.ok)
     return fail(DCOR_EINVAL, "%s: scratch bytes overflow (p = %lld, n = %lld)", entry, (long long)t->p,
                 (long long)t->n);
-  plan.lohi.resize(2 * (size_t)t->p);
-  for (int64_t c = 0; c < t->p; ++c) { plan.lohi[2 * (size_t)c] = t->lo[c]; plan.lohi[2 * (size_t)c + 1] = t->hi[c]; }
-  plan.pv.eps_mean = t->eps_mean; plan.pv.eps_m2 = t->eps_m2;
-  plan.pv.k0 = (uint32_t)t->seed_std; plan.pv.k1 = (uint32_t)(t->seed_std >> 32);
+  private_release_plan(*t, plan.lohi, plan.pv);
   return DCOR_OK;
 }
 
@@ -616,18 +674,13 @@ int plan_hrs_table_pairwise(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair
   if (int st = segment_heads(entry, segs, nseg, t->p, &plan.items)) return st;
   // every segment's pair, then its launch constants: those of the reference call on the pair's
   // n_ab compacted rows, lam and eps
-  struct Pair { int64_t n_ab, slot; };   // slot: -1 until a segment with replicates names the pair
-  std::map<std::pair<int32_t, int32_t>, Pair> seen;
+  PairSlots pairs;
   int64_t first = 0;
   for (int64_t i = 0; i < nseg; ++i) {
     const dcor_hrs_pair_segment& g = segs[i];
-    const auto at = seen.emplace(std::make_pair(g.col_x, g.col_y), Pair{0, -1});
-    Pair& pr = at.first->second;
-    if (at.second) pr.n_ab = hrs_pair_count(t->valid, t->n, g.col_x, g.col_y);
-    if (pr.n_ab < 2 || pr.n_ab > DCOR_DICT_NMAX)
-      return fail(DCOR_EINVAL, "%s: segment %lld: columns (%d, %d) have n_ab = %lld pairwise-complete rows, "
-                  "must be in [2, %d]: a replicate keeps u16 indices of the compacted rows in LDS", entry,
-                  (long long)i, (int)g.col_x, (int)g.col_y, (long long)pr.n_ab, DCOR_DICT_NMAX);
+    PairSlots::Pair* prp;
+    if (int st = pairs.checked(entry, t->valid, t->n, g, i, &prp)) return st;
+    PairSlots::Pair& pr = *prp;
     dcor_hrs_table_desc u;   // the reference call's table: the pair's own count and delta (rds:199)
     std::memset(&u, 0, sizeof(u));
     u.n = pr.n_ab; u.p = t->p; u.ld = t->ld; u.D = t->D; u.lam = t->lam;
@@ -637,22 +690,14 @@ int plan_hrs_table_pairwise(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair
     if (int st = premat_subg_const(&q, pc)) return st;
     if (g.reps == 0) continue;
     if (tab.empty()) { plan.c0 = pc; plan.c0.X = plan.c0.Y = nullptr; }
-    if (pr.slot < 0) {   // a pair not run before: its panel follows the others'
-      HrsPairSlot sl;
-      std::memset(&sl, 0, sizeof(sl));
-      sl.n_ab = pr.n_ab; sl.panel = plan.panel_elems;
-      sl.col_x = g.col_x; sl.col_y = g.col_y;
-      plan.panel_elems += hrs_pair_panel_elems(pr.n_ab);
-      pr.slot = (int64_t)slots.size();
-      slots.push_back(sl);
-    }
+    const HrsPairSlot& sl = pairs.slot(pr, g, slots, plan.panel_elems);
     HrsPairNaSegConst r;
     std::memset(&r, 0, sizeof(r));
     hrs_segment_record(pc, g, first, r);
     r.col_x = g.col_x; r.col_y = g.col_y;
     r.n = pc.s.n; r.nd = pc.s.nd; r.sqrt_n = pc.s.sqrt_n;
     hrs_feistel_split(pc.s.n, &r.pa, &r.pc);
-    r.panel = slots[(size_t)pr.slot].panel;
+    r.panel = sl.panel;
     first += g.reps;
     tab.push_back(r);
     plan.max_km = std::max(plan.max_km, pc.s.k * (int64_t)pc.s.m);
@@ -661,6 +706,65 @@ int plan_hrs_table_pairwise(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair
   if (!plan.lay.ok)
     return fail(DCOR_EINVAL, "%s: scratch bytes overflow (p = %lld, n = %lld)", entry, (long long)t->p,
                 (long long)t->n);
+  return DCOR_OK;
+}
+
+int plan_hrs_private_pairwise(const dcor_hrs_private_na_desc* t, const dcor_hrs_pair_segment* segs,
+                              int64_t nseg, HrsPrivPairPlan& plan) {
+  const char* const entry = "hrs_private_pairwise";
+  plan = HrsPrivPairPlan();
+  auto &tab = plan.tab; auto &slots = plan.slots;
+  if (!t->D || !t->lo || !t->hi || !t->valid)
+    return fail(DCOR_EINVAL, "%s: null argument (D, lo, hi, valid)", entry);
+  if (t->n < 2 || t->n > 0x7fffffffLL)
+    return fail(DCOR_EINVAL, "%s: n must be in [2, 2^31) (got %lld)", entry, (long long)t->n);
+  if (int st = table_shape(entry, *t)) return st;
+  if (!HrsPrivPairLayout::columns(t->n, t->p).ok)
+    return fail(DCOR_EINVAL, "%s: p * ceil(n / 64) * 8 scratch bytes overflow (p = %lld, n = %lld)", entry,
+                (long long)t->p, (long long)t->n);
+  if (int st = private_release_args(entry, *t)) return st;
+  if (!(t->delta > 0.0) && !std::isnan(t->delta))
+    return fail(DCOR_EINVAL, "%s: delta must be positive, or NaN for 1 / n_ab per pair", entry);
+  if (int st = check_alpha_nsim(t->n, t->alpha, t->nsim)) return st;
+  if (int st = segment_heads(entry, segs, nseg, t->p, &plan.items)) return st;
+  // every segment's pair, then its record: the private entry's at the pair's n_ab and delta
+  PairSlots pairs;
+  int64_t first = 0;
+  for (int64_t i = 0; i < nseg; ++i) {
+    const dcor_hrs_pair_segment& g = segs[i];
+    PairSlots::Pair* pr;
+    if (int st = pairs.checked(entry, t->valid, t->n, g, i, &pr)) return st;
+    const double delta = std::isnan(t->delta) ? 1.0 / (double)pr->n_ab : t->delta;   // rds:199
+    PrematSubgConst pc;
+    HrsPrivNaSegConst r;
+    std::memset(&r, 0, sizeof(r));
+    if (int st = private_segment_record(pr->n_ab, delta, t->alpha, t->nsim, g, first, pc, r)) return st;
+    if (g.reps == 0) continue;
+    if (tab.empty()) private_call_consts(pc, plan.c0);
+    r.n = pc.s.n; r.nd = pc.s.nd; r.sqrt_n = pc.s.sqrt_n;
+    hrs_feistel_split(pc.s.n, &r.pa, &r.pc);
+    r.panel = pairs.slot(*pr, g, slots, plan.panel_elems).panel;
+    r.n_x = (double)hrs_pair_count(t->valid, t->n, g.col_x, g.col_x);   // dp_sd's own n (rds:74)
+    r.n_y = (double)hrs_pair_count(t->valid, t->n, g.col_y, g.col_y);
+    first += g.reps;
+    tab.push_back(r);
+    plan.max_km = std::max(plan.max_km, pc.s.k * (int64_t)pc.s.m);
+  }
+  if (!tab.empty()) {   // every column's count and the place of its compacted copy
+    plan.cols.resize((size_t)t->p);
+    for (int64_t c = 0; c < t->p; ++c) {
+      HrsPrivCol& q = plan.cols[(size_t)c];
+      q.n_c = hrs_pair_count(t->valid, t->n, c, c);
+      q.off = plan.comp_elems;
+      plan.comp_elems += hrs_priv_col_elems(q.n_c);
+    }
+  }
+  plan.lay = HrsPrivPairLayout(plan.items, (int64_t)tab.size(), (int64_t)slots.size(), t->n, t->p,
+                               plan.comp_elems, plan.panel_elems);
+  if (!plan.lay.ok)
+    return fail(DCOR_EINVAL, "%s: scratch bytes overflow (p = %lld, n = %lld)", entry, (long long)t->p,
+                (long long)t->n);
+  private_release_plan(*t, plan.lohi, plan.pv);
   return DCOR_OK;
 }
 

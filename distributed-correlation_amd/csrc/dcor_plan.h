@@ -1,6 +1,6 @@
 // dcor_plan.h -- the host decisions that need no device: the error reporter, the argument checks,
 // every launch constant (R operation order, cited), the scratch layouts (dcor_layout.h) and the
-// segment planners of the nine segment-list entries, one plan struct each.  Plain C++: neither
+// segment planners of the ten segment-list entries, one plan struct each.  Plain C++: neither
 // this header nor dcor_plan.cpp includes the HIP runtime, so the unit compiles, runs and is
 // sanitized with a host compiler alone (tests/host/*.cpp over tests/host/check.h).  Not part of
 // the ABI.
@@ -106,7 +106,7 @@ struct HrsFusedSweepPlan {
 int plan_hrs_fused_sweep(const dcor_premat_subg* base, const dcor_panel* panel,
                          const dcor_hrs_segment* segs, int64_t nseg, HrsFusedSweepPlan& plan);
 
-// ---- the seven table entries: int plan_X(desc, segs, nseg, XPlan&).  A planner resets its plan and
+// ---- the eight table entries: int plan_X(desc, segs, nseg, XPlan&).  A planner resets its plan and
 // makes every check of its entry after the null checks of the descriptor, segs and d_out, in the
 // order include/dcor.h documents; a segment without replicates is checked too.  On DCOR_OK the plan
 // is all the entry needs: tab, the records of the segments with reps > 0 in call order; items, the
@@ -168,6 +168,25 @@ struct HrsPairTablePlan : TablePlan<HrsPairNaSegConst, HrsPairTableLayout> {
 };
 int plan_hrs_table_pairwise(const dcor_hrs_table_na_desc* t, const dcor_hrs_pair_segment* segs,
                             int64_t nseg, HrsPairTablePlan& plan);
+
+// dcor_hrs_private_pairwise_launch.  slots, panel_elems: plan_hrs_table_pairwise's slot table (the
+// distinct ordered pairs, n_ab, the panel's first element).  A record is plan_hrs_private's at n =
+// n_ab and delta = t->delta or 1 / n_ab (log_inv_delta follows), with n_ab, nd, sqrt_n, the Feistel
+// split and the slot's panel as plan_hrs_table_pairwise's record, and the two columns' own counts n_x,
+// n_y = popcount(valid[c]) as the doubles the release divides by.  cols: every column's count and the
+// first element of its compacted copy (hrs_priv_col_elems apart; comp_elems in all); lohi, pv: as
+// plan_hrs_private's; c0: crit, mix, hrs (n, nd, sqrt_n are the first kept segment's: the records
+// carry their own).
+struct HrsPrivPairPlan : TablePlan<HrsPrivNaSegConst, HrsPrivPairLayout> {
+  std::vector<HrsPairSlot> slots;
+  std::vector<HrsPrivCol> cols;
+  std::vector<double> lohi;
+  HrsPrivCall pv{};
+  PrematSubgConst c0{};
+  int64_t max_km = 0, panel_elems = 0, comp_elems = 0;
+};
+int plan_hrs_private_pairwise(const dcor_hrs_private_na_desc* t, const dcor_hrs_pair_segment* segs,
+                              int64_t nseg, HrsPrivPairPlan& plan);
 
 // dcor_subg_panel_launch.  A record holds, field for field, what make_subg yields for (n, eps1, eps2,
 // eta1, eta2, alpha, hrs = 0, nsim).  slots: the distinct batch sizes m of the kept segments in order

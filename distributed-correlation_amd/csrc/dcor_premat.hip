@@ -2249,14 +2249,22 @@ struct HrsAffineLoad {
 
 // A segment's fields that do not change with the replicate (hrs_seg_load's without the lambda-
 // dependent ones, which the table holds as zeros).
-__device__ __forceinline__ void hrs_private_seg_load(SegTab<HrsPrivSegConst> tab, int s, PrematSubgConst& p,
-                                                     HrsKeys& hk) {
+template <class Seg>
+__device__ __forceinline__ void hrs_private_seg_load(SegTab<Seg> tab, int s, PrematSubgConst& p, HrsKeys& hk) {
   SubgConst& c = p.s;
   c.k = tab[s].k; c.m = tab[s].m; c.md_pow2 = tab[s].md_pow2;
   c.md = tab[s].md; c.kd = tab[s].kd; c.inv_md = tab[s].inv_md;
   c.m_over_k = tab[s].m_over_k; c.sqrt_k = tab[s].sqrt_k; c.eps_r = tab[s].eps_r;
   hk.ni0 = tab[s].ni0; hk.ni1 = tab[s].ni1; hk.in0 = tab[s].in0; hk.in1 = tab[s].in1;
   hk.rep_begin = tab[s].rep_begin;
+}
+// The private pairwise entry's record: the segment's own sample count and what follows from it as
+// well, as hrs_seg_load takes them from the pairwise record.
+__device__ __forceinline__ void hrs_private_seg_load(SegTab<HrsPrivNaSegConst> tab, int s, PrematSubgConst& p,
+                                                     HrsKeys& hk) {
+  hrs_private_seg_load<HrsPrivNaSegConst>(tab, s, p, hk);
+  p.s.n = tab[s].n; p.s.nd = tab[s].nd; p.s.sqrt_n = tab[s].sqrt_n;
+  hk.pa = tab[s].pa; hk.pc = tab[s].pc;
 }
 
 // What a segment's pair brings to every one of its replicates: the columns' intervals and means and
@@ -2266,8 +2274,8 @@ struct HrsPrivPair {
   double log_inv_delta, crit_sqrt2;
   uint32_t col_a, col_b;
 };
-__device__ __forceinline__ HrsPrivPair hrs_private_pair(SegTab<HrsPrivSegConst> tab, int s,
-                                                        const double* __restrict__ lohi,
+template <class Seg>
+__device__ __forceinline__ HrsPrivPair hrs_private_pair(SegTab<Seg> tab, int s, const double* __restrict__ lohi,
                                                         const double* __restrict__ m12) {
   HrsPrivPair q;
   q.col_a = (uint32_t)tab[s].col_x; q.col_b = (uint32_t)tab[s].col_y;
@@ -2299,14 +2307,18 @@ __device__ __forceinline__ double wave_uniform(double x) {
 // with nothing to synchronise; neither has been timed.  What the replicate's loops read (the map's
 // four scalars, bx, by, bs, lr) leaves through wave_uniform, so the loops hold them as k_hrs_table
 // holds its table constants, in scalar registers.
-__device__ __forceinline__ void hrs_private_item(const HrsPrivCall& pv, const HrsPrivPair& q, uint32_t rep,
-                                                 PrematSubgConst& p, HrsPriv& ra, HrsPriv& rb) {
+// nd_a, nd_b: the counts the two releases divide by -- the samples m1, m2 are the means of: the
+// table's n in the private entry, each column's own present rows in the private pairwise entry --
+// while hrs_lambda_consts takes the pair's count c.nd.
+__device__ __forceinline__ void hrs_private_item(const HrsPrivCall& pv, const HrsPrivPair& q, double nd_a,
+                                                 double nd_b, uint32_t rep, PrematSubgConst& p, HrsPriv& ra,
+                                                 HrsPriv& rb) {
   SubgConst& c = p.s;
   const U4 wa = draw(q.col_a, rep, DCOR_SITE_STD, pv.k0, pv.k1);
   const U4 wb = draw(q.col_b, rep, DCOR_SITE_STD, pv.k0, pv.k1);
-  ra = hrs_private_release(q.m1_a, q.m2_a, q.lo_a, q.hi_a, c.nd, pv.eps_mean, pv.eps_m2,
+  ra = hrs_private_release(q.m1_a, q.m2_a, q.lo_a, q.hi_a, nd_a, pv.eps_mean, pv.eps_m2,
                            unit_laplace(u53(wa.w0, wa.w1)), unit_laplace(u53(wa.w2, wa.w3)));
-  rb = hrs_private_release(q.m1_b, q.m2_b, q.lo_b, q.hi_b, c.nd, pv.eps_mean, pv.eps_m2,
+  rb = hrs_private_release(q.m1_b, q.m2_b, q.lo_b, q.hi_b, nd_b, pv.eps_mean, pv.eps_m2,
                            unit_laplace(u53(wb.w0, wb.w1)), unit_laplace(u53(wb.w2, wb.w3)));
   const HrsLamConst lc = hrs_lambda_consts(ra.lam, rb.lam, c.eps_r, c.md, c.nd, q.log_inv_delta, q.crit_sqrt2);
   ra.mean = wave_uniform(ra.mean); ra.den = wave_uniform(ra.den);
@@ -2342,7 +2354,7 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_private_table(PrematSubgCo
     // than held across the replicate's loops, which need the registers
     const HrsPrivPair q = hrs_private_pair(tab, seg, lohi, m12);
     HrsPriv ra, rb;
-    hrs_private_item(pv, q, rep, p, ra, rb);
+    hrs_private_item(pv, q, p.s.nd, p.s.nd, rep, p, ra, rb);
     const HrsAffineLoad ld{cols + (int64_t)q.col_a * pitch, cols + (int64_t)q.col_b * pitch, ra.mean, ra.den,
                            rb.mean, rb.den};
     hrs_fused_l2_item(p, hk, rep, ld, gs, red, par, part + it);
@@ -2351,16 +2363,27 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_private_table(PrematSubgCo
 
 // k_hrs_sweep_fused_epilogue for that entry: the replicate's constants again, with the same
 // function (cheaper than carrying them: no scratch), then the shared epilogue item; the release
-// goes to priv when the caller asked for it.
+// goes to priv when the caller asked for it.  Seg: the table's record (HrsPrivSegConst, or the private
+// pairwise entry's HrsPrivNaSegConst with its own n and column counts).
+// The counts segment s's two releases divide by, after its loader has run.
+__device__ __forceinline__ void hrs_private_counts(SegTab<HrsPrivSegConst>, int, const PrematSubgConst& p,
+                                                   double& nd_a, double& nd_b) {
+  nd_a = nd_b = p.s.nd;
+}
+__device__ __forceinline__ void hrs_private_counts(SegTab<HrsPrivNaSegConst> tab, int s, const PrematSubgConst&,
+                                                   double& nd_a, double& nd_b) {
+  nd_a = tab[s].n_x; nd_b = tab[s].n_y;
+}
+template <class Seg>
 __global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_private_epilogue(PrematSubgConst p, HrsPrivCall pv,
-                                                                     const HrsPrivSegConst* __restrict__ tab_g,
+                                                                     const Seg* __restrict__ tab_g,
                                                                      int nseg, const double* __restrict__ lohi,
                                                                      const double* __restrict__ m12,
                                                                      const SubgPartial* __restrict__ part,
                                                                      dcor_rep_out* out, double* __restrict__ priv) {
   __shared__ SelScratch sel;
   __shared__ double bc[2];
-  const SegTab<HrsPrivSegConst> tab = (SegTab<HrsPrivSegConst>)tab_g;
+  const SegTab<Seg> tab = (SegTab<Seg>)tab_g;
   const int64_t r = blockIdx.x;
   HrsKeys hk{0, 0, 0, 0, 0, 0, 0};   // the epilogue draws no permutation: pa, pc unused
   const int s = __builtin_amdgcn_readfirstlane(seg_find(tab, nseg, r));
@@ -2369,8 +2392,10 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_private_epilogue(PrematSubgC
   const int64_t j = r - tab[s].first;
   const int64_t row = tab[s].out_row + j;
   const uint32_t rep = hk.rep_begin + (uint32_t)j;
+  double nd_a, nd_b;
+  hrs_private_counts(tab, s, p, nd_a, nd_b);
   HrsPriv ra, rb;
-  hrs_private_item(pv, q, rep, p, ra, rb);
+  hrs_private_item(pv, q, nd_a, nd_b, rep, p, ra, rb);
   if (priv != nullptr && threadIdx.x == 0) {
     double* d = priv + 6 * row;
     d[0] = ra.mean; d[1] = ra.sd; d[2] = ra.lam;
@@ -2385,32 +2410,20 @@ __global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_private_epilogue(PrematSubgC
 // pair: the pair's rows compacted into a packed panel, which k_hrs_pair_table gathers as
 // k_hrs_sweep_fused_l2 gathers k_premat_xy_pack's.
 
-// One workgroup per slot (a distinct ordered pair of the call): an order-preserving compaction of
-// the rows of ok = valid[col_x] & valid[col_y] into the slot's panel, the sample of rank r as
-// (rclip(D[col_x][i], lam[col_x]), rclip(D[col_y][i], lam[col_y])) -- k_premat_xy_pack's bits for
-// xyc and, X being the sender under one bound per column, for soc.  HRS_PACK_NT mask words (64 rows
-// each) per trip: a word's first rank is the running base plus the exclusive scan of the words'
-// popcounts (DPP within a wave, the wave totals through LDS), and row i of a word has rank first +
-// popcount(word & ((1 << (i & 63)) - 1)).  A rank has one writer: no atomics.  Rows at i >= n are
-// masked out of the last word, so D is read at present rows only; the host has checked the same
-// masks' count n_ab <= 65536, which bounds every rank.  The element after an odd n_ab is zero.
+// An order-preserving compaction of the rows of ok = ma & mb (two masks of nw words; ma == mb: one
+// column's own rows) by one workgroup of HRS_PACK_NT threads: emit(i, r) once for every row i of ok,
+// r its rank.  HRS_PACK_NT mask words (64 rows each) per trip: a word's first rank is the running
+// base plus the exclusive scan of the words' popcounts (DPP within a wave, the wave totals through
+// LDS), and row i of a word has rank first + popcount(word & ((1 << (i & 63)) - 1)).  A rank has one
+// caller: no atomics.  Rows at i >= n are masked out of the last word, so emit sees present rows only.
+// Ranks are 32-bit: n < 2^31 (the host's check).
 #define HRS_PACK_NT 256
-__global__ __launch_bounds__(HRS_PACK_NT) void k_hrs_pair_pack(const double* __restrict__ D, int64_t ld,
-                                                               int64_t n, int64_t nw,
-                                                               const double* __restrict__ lam,
-                                                               const uint64_t* __restrict__ masks,
-                                                               const HrsPairSlot* __restrict__ slots,
-                                                               double2* __restrict__ panels) {
+template <class Emit>
+__device__ __forceinline__ void hrs_mask_compact(const uint64_t* __restrict__ ma, const uint64_t* __restrict__ mb,
+                                                 int64_t n, int64_t nw, Emit emit) {
   __shared__ uint64_t sw[HRS_PACK_NT];            // the trip's ANDed words
   __shared__ uint32_t sp[HRS_PACK_NT];            // each word's first rank
   __shared__ uint32_t wtot[HRS_PACK_NT / 64];
-  const HrsPairSlot sl = slots[blockIdx.x];
-  const double* __restrict__ xa = D + (int64_t)sl.col_x * ld;
-  const double* __restrict__ xb = D + (int64_t)sl.col_y * ld;
-  const uint64_t* __restrict__ ma = masks + (int64_t)sl.col_x * nw;
-  const uint64_t* __restrict__ mb = masks + (int64_t)sl.col_y * nw;
-  const double la = lam[sl.col_x], lb = lam[sl.col_y];
-  double2* __restrict__ dst = panels + sl.panel;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   uint32_t base = 0;
   for (int64_t w0 = 0; w0 < nw; w0 += HRS_PACK_NT) {
@@ -2439,14 +2452,45 @@ __global__ __launch_bounds__(HRS_PACK_NT) void k_hrs_pair_pack(const double* __r
     for (int j = 0; j < 64 && row0 + (int64_t)j * HRS_PACK_NT < n; ++j) {
       const int q = j * (HRS_PACK_NT / 64) + wv;
       const uint64_t wd = sw[q];
-      if ((wd >> lane) & 1ull) {
-        const int64_t i = row0 + (int64_t)j * HRS_PACK_NT + tid;
-        const uint32_t r = sp[q] + (uint32_t)__popcll(wd & ((1ull << lane) - 1ull));
-        if ((int64_t)r < sl.n_ab) dst[r] = make_double2(rclip(xa[i], la), rclip(xb[i], lb));
-      }
+      if ((wd >> lane) & 1ull)
+        emit(row0 + (int64_t)j * HRS_PACK_NT + tid, sp[q] + (uint32_t)__popcll(wd & ((1ull << lane) - 1ull)));
     }
   }
-  if (tid == 0 && (sl.n_ab & 1)) dst[sl.n_ab] = make_double2(0.0, 0.0);
+}
+
+// One workgroup per slot (a distinct ordered pair of the call): the rows of ok = valid[col_x] &
+// valid[col_y] compacted in order (hrs_mask_compact) into the slot's panel.  LOHI = false, bnd = lam
+// [p]: the sample of rank r is (rclip(D[col_x][i], lam[col_x]), rclip(D[col_y][i], lam[col_y])) --
+// k_premat_xy_pack's bits for xyc and, X being the sender under one bound per column, for soc.
+// LOHI = true, bnd = (lo, hi) [p]: the raw columns clipped to their intervals (rclip_lohi), the
+// values the private entries' affine map takes.  D is read at present rows only; the host has checked
+// the same masks' count n_ab <= 65536, which bounds every rank.  The element after an odd n_ab is zero.
+template <bool LOHI>
+struct HrsPackClip {   // column c's clip, its bound(s) read once
+  double a, b;
+  __device__ __forceinline__ HrsPackClip(const double* __restrict__ bnd, int32_t c)
+      : a(LOHI ? bnd[2 * c] : bnd[c]), b(LOHI ? bnd[2 * c + 1] : 0.0) {}
+  __device__ __forceinline__ double operator()(double x) const {
+    if constexpr (LOHI) return rclip_lohi(x, a, b);
+    else return rclip(x, a);
+  }
+};
+template <bool LOHI>
+__global__ __launch_bounds__(HRS_PACK_NT) void k_hrs_pair_pack(const double* __restrict__ D, int64_t ld,
+                                                               int64_t n, int64_t nw,
+                                                               const double* __restrict__ bnd,
+                                                               const uint64_t* __restrict__ masks,
+                                                               const HrsPairSlot* __restrict__ slots,
+                                                               double2* __restrict__ panels) {
+  const HrsPairSlot sl = slots[blockIdx.x];
+  const double* __restrict__ xa = D + (int64_t)sl.col_x * ld;
+  const double* __restrict__ xb = D + (int64_t)sl.col_y * ld;
+  double2* __restrict__ dst = panels + sl.panel;
+  const HrsPackClip<LOHI> ca(bnd, sl.col_x), cb(bnd, sl.col_y);
+  hrs_mask_compact(masks + (int64_t)sl.col_x * nw, masks + (int64_t)sl.col_y * nw, n, nw, [&](int64_t i, uint32_t r) {
+    if ((int64_t)r < sl.n_ab) dst[r] = make_double2(ca(xa[i]), cb(xb[i]));
+  });
+  if (threadIdx.x == 0 && (sl.n_ab & 1)) dst[sl.n_ab] = make_double2(0.0, 0.0);
 }
 
 // k_hrs_table's persistent shell over the pairwise record: on entering a segment its n, nd, sqrt_n,
@@ -2474,6 +2518,95 @@ __global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_pair_table(PrematSubgConst
       ld.xyc = ld.soc = panels + tab[s].panel;
     });
     hrs_fused_l2_item(p, hk, hk.rep_begin + (uint32_t)(it - cur.first), ld, gs, red, par, part + it);
+  }
+}
+
+// ------- the private standardisation per replicate on the pairwise-complete cases of such a table ---
+// dcor_hrs_private_pairwise_launch: the two entries above composed.  A column's release comes from
+// its own present rows (dp_sd drops a column's own NA, real-data-sims.R:74), a pair's samples,
+// geometry and lambda-dependent constants from the rows present in both (:119-120, :187-189).
+
+// One workgroup per column c: its present rows compacted in row order (hrs_mask_compact under the
+// column's one mask) to comp + cols[c].off, the raw values.  dp_clip_means is thread-strided over
+// the index -- thread t sums the elements t, t + 256, ... -- so the means of the column without its
+// gaps carry dcor_dp_sd's bits only when they are summed over the compacted copy; a masked loop over
+// the rows would deal the samples to other threads.  D is read at present rows only; the host has
+// counted the same mask (cols[c].n_c), which bounds every rank.
+__global__ __launch_bounds__(HRS_PACK_NT) void k_hrs_col_compact(const double* __restrict__ D, int64_t ld,
+                                                                 int64_t n, int64_t nw,
+                                                                 const uint64_t* __restrict__ masks,
+                                                                 const HrsPrivCol* __restrict__ cols,
+                                                                 double* __restrict__ comp) {
+  const int64_t c = blockIdx.x;
+  const HrsPrivCol cl = cols[c];
+  const double* __restrict__ src = D + c * ld;
+  double* __restrict__ dst = comp + cl.off;
+  const uint64_t* __restrict__ m = masks + c * nw;
+  hrs_mask_compact(m, m, n, nw, [&](int64_t i, uint32_t r) {
+    if ((int64_t)r < cl.n_c) dst[r] = src[i];
+  });
+}
+
+// One workgroup of DCOR_BLOCK threads per column c: k_dp_sd's means (dp_clip_means) of its compacted
+// copy clipped to [lohi[2 c], lohi[2 c + 1]] to m12[2 c], m12[2 c + 1].  A launch of its own: the copy
+// is another launch's output, read through ordinary loads.
+__global__ __launch_bounds__(DCOR_BLOCK) void k_hrs_col_means(const HrsPrivCol* __restrict__ cols,
+                                                              const double* __restrict__ comp,
+                                                              const double* __restrict__ lohi,
+                                                              double* __restrict__ m12) {
+  __shared__ double red[16 * DCOR_WAVES];
+  const int64_t c = blockIdx.x;
+  const HrsPrivCol cl = cols[c];
+  double m1, m2;
+  dp_clip_means(comp + cl.off, cl.n_c, lohi[2 * c], lohi[2 * c + 1], red, &m1, &m2);
+  if (threadIdx.x == 0) { m12[2 * c] = m1; m12[2 * c + 1] = m2; }
+}
+
+// HrsPackedLoad with the replicate's affine map applied at gather time, as HrsAffineLoad applies it
+// to two columns: the pair's panel holds (clip(x, lo_x, hi_x), clip(y, lo_y, hi_y)) and X is the
+// sender, so xy and so are the same values.
+struct HrsPackedAffineLoad {
+  const double2* __restrict__ xyc;
+  double mean_a, den_a, mean_b, den_b;
+  __device__ __forceinline__ double2 map(double2 v) const {
+    return make_double2((v.x - mean_a) / den_a, (v.y - mean_b) / den_b);
+  }
+  __device__ __forceinline__ double2 xy(uint32_t i) const { return map(xyc[i]); }
+  __device__ __forceinline__ double2 so(int64_t i) const { return map(xyc[i]); }
+  __device__ __forceinline__ void so2(int64_t b, double2& v0, double2& v1) const {
+    v0 = map(xyc[2 * b]); v1 = map(xyc[2 * b + 1]);
+  }
+};
+
+// k_hrs_pair_table's persistent shell (a segment's n, split and panel at a workgroup-uniform address)
+// around k_hrs_private_table's item: the replicate's two releases from the columns' own counts, its
+// constants at the pair's n_ab, then hrs_fused_l2_item on the pair's panel through the affine map.
+template <int WPE>
+__global__ __launch_bounds__(DICT_NT, WPE) void k_hrs_private_pair_table(
+    PrematSubgConst p, HrsPrivCall pv, const HrsPrivNaSegConst* __restrict__ tab_g, int nseg, int64_t items,
+    const double* __restrict__ lohi, const double* __restrict__ m12, const double2* __restrict__ panels,
+    SubgPartial* __restrict__ part) {
+  extern __shared__ double dsm[];
+  double* red = dsm;
+  uint16_t* gs = reinterpret_cast<uint16_t*>(dsm + 20 * DICT_NW);  // the largest k m of the segments
+  const SegTab<HrsPrivNaSegConst> tab = (SegTab<HrsPrivNaSegConst>)tab_g;
+  HrsKeys hk{0, 0, 0, 0, 0, 0, 0};
+  SegCursor cur;
+  int seg = 0, par = 0;
+  for (int64_t it = blockIdx.x; it < items; it += gridDim.x, par ^= 1) {
+    cur.seek(tab, nseg, items, it, [&](int s) {
+      hrs_private_seg_load(tab, s, p, hk);
+      seg = s;
+    });
+    const uint32_t rep = hk.rep_begin + (uint32_t)(it - cur.first);
+    // as k_hrs_private_table: the pair's intervals, means and counts are read again for every item
+    const HrsPrivPair q = hrs_private_pair(tab, seg, lohi, m12);
+    double nd_a, nd_b;
+    hrs_private_counts(tab, seg, p, nd_a, nd_b);
+    HrsPriv ra, rb;
+    hrs_private_item(pv, q, nd_a, nd_b, rep, p, ra, rb);
+    const HrsPackedAffineLoad ld{panels + tab[seg].panel, ra.mean, ra.den, rb.mean, rb.den};
+    hrs_fused_l2_item(p, hk, rep, ld, gs, red, par, part + it);
   }
 }
 
@@ -2631,7 +2764,7 @@ int launch_hrs_private_table(const PrematSubgConst& c, const HrsPrivCall& pv, co
                      c.s.n, npad, lohi, m12, cols);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c, pv, pa, pc, tab,
                      nseg, items, lohi, (const double*)m12, (const double*)cols, npad, (SubgPartial*)part);
-  hipLaunchKernelGGL(k_hrs_private_epilogue, dim3((unsigned)items), dim3(DCOR_BLOCK), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_hrs_private_epilogue<HrsPrivSegConst>, dim3((unsigned)items), dim3(DCOR_BLOCK), 0, (hipStream_t)stream,
                      c, pv, tab, nseg, lohi, (const double*)m12, (const SubgPartial*)part, out, priv);
   return (int)hipGetLastError();
 }
@@ -2647,12 +2780,40 @@ int launch_hrs_pair_table(const PrematSubgConst& c, const double* D, int64_t n, 
   const PairK kern = wsel == 4 ? k_hrs_pair_table<4> : k_hrs_pair_table<6>;
   int64_t grid = 0;
   if (int e = persistent_grid((const void*)kern, DICT_NT, lds, items, &grid, kLdsDynMax)) return e;
-  hipLaunchKernelGGL(k_hrs_pair_pack, dim3((unsigned)nslot), dim3(HRS_PACK_NT), 0, (hipStream_t)stream, D, ld,
+  hipLaunchKernelGGL(k_hrs_pair_pack<false>, dim3((unsigned)nslot), dim3(HRS_PACK_NT), 0, (hipStream_t)stream, D, ld,
                      n, nw, lam, masks, slots, panels);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c, tab, nseg, items,
                      (const double2*)panels, (SubgPartial*)part);
   hipLaunchKernelGGL(k_hrs_sweep_fused_epilogue<HrsPairNaSegConst>, dim3((unsigned)items), dim3(DCOR_BLOCK), 0,
                      (hipStream_t)stream, c, tab, nseg, (const SubgPartial*)part, out);
+  return (int)hipGetLastError();
+}
+
+int launch_hrs_private_pair_table(const PrematSubgConst& c, const HrsPrivCall& pv, const double* D, int64_t p,
+                                  int64_t n, int64_t ld, const double* lohi, const uint64_t* masks, int64_t nw,
+                                  const HrsPrivCol* cols, double* comp, double* m12, const HrsPairSlot* slots,
+                                  int nslot, double2* panels, const HrsPrivNaSegConst* tab, int nseg,
+                                  int64_t items, int64_t max_km, void* part, dcor_rep_out* out, double* priv,
+                                  void* stream) {
+  if (items <= 0 || nseg <= 0 || nslot <= 0 || p <= 0) return 0;
+  const int wsel = hrs_wpe();
+  const size_t lds = hrs_l2_lds_bytes(max_km);   // k_hrs_pair_table's threads and LDS
+  typedef void (*PrivPairK)(PrematSubgConst, HrsPrivCall, const HrsPrivNaSegConst*, int, int64_t, const double*,
+                            const double*, const double2*, SubgPartial*);
+  const PrivPairK kern = wsel == 4 ? k_hrs_private_pair_table<4> : k_hrs_private_pair_table<6>;
+  int64_t grid = 0;
+  if (int e = persistent_grid((const void*)kern, DICT_NT, lds, items, &grid, kLdsDynMax)) return e;
+  hipLaunchKernelGGL(k_hrs_col_compact, dim3((unsigned)p), dim3(HRS_PACK_NT), 0, (hipStream_t)stream, D, ld, n, nw,
+                     masks, cols, comp);
+  hipLaunchKernelGGL(k_hrs_col_means, dim3((unsigned)p), dim3(DCOR_BLOCK), 0, (hipStream_t)stream, cols,
+                     (const double*)comp, lohi, m12);
+  hipLaunchKernelGGL(k_hrs_pair_pack<true>, dim3((unsigned)nslot), dim3(HRS_PACK_NT), 0, (hipStream_t)stream, D, ld,
+                     n, nw, lohi, masks, slots, panels);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(DICT_NT), lds, (hipStream_t)stream, c, pv, tab, nseg, items,
+                     lohi, (const double*)m12, (const double2*)panels, (SubgPartial*)part);
+  hipLaunchKernelGGL(k_hrs_private_epilogue<HrsPrivNaSegConst>, dim3((unsigned)items), dim3(DCOR_BLOCK), 0,
+                     (hipStream_t)stream, c, pv, tab, nseg, lohi, (const double*)m12, (const SubgPartial*)part, out,
+                     priv);
   return (int)hipGetLastError();
 }
 

@@ -1,8 +1,9 @@
 // dcor_segtab.h -- the device side of a segment-table launch (dcor_hrs_fused_sweep_launch,
 // dcor_sign_panel_launch, dcor_sign_table_launch, dcor_hrs_table_launch,
-// dcor_hrs_table_pairwise_launch, dcor_subg_panel_launch, dcor_subg_table_launch): a persistent grid whose work unit u takes items u, u + units, ... and
-// reads the constants of the segment an item belongs to from a device table the host planner built
-// (dcor_plan.cpp).
+// dcor_hrs_table_pairwise_launch, dcor_hrs_private_table_launch, dcor_hrs_private_pairwise_launch,
+// dcor_subg_panel_launch, dcor_subg_table_launch): a persistent grid whose work unit u takes items u,
+// u + units, ... and reads the constants of the segment an item belongs to from a device table the
+// host planner built (dcor_plan.cpp).
 //
 // The table contract, for every record type Seg: `first` (the segment's first item) is strictly
 // increasing with tab[0].first == 0, so only segments with reps > 0 are present and segment s holds

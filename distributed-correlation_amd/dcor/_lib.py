@@ -164,6 +164,14 @@ class HrsPrivateDesc(C.Structure):
                 ("alpha", C.c_double), ("delta", C.c_double), ("nsim", C.c_int64)]
 
 
+class HrsPrivateNaDesc(C.Structure):
+    """dcor_hrs_private_na_desc (include/dcor.h): dcor_hrs_private_desc and the columns' presence masks
+    (a HOST array of p x ceil(n / 64) words, as HrsTableNaDesc's)."""
+    _fields_ = [("n", C.c_int64), ("p", C.c_int64), ("ld", C.c_int64), ("D", _P), ("lo", _D), ("hi", _D),
+                ("valid", C.POINTER(C.c_uint64)), ("eps_mean", C.c_double), ("eps_m2", C.c_double),
+                ("seed_std", C.c_uint64), ("alpha", C.c_double), ("delta", C.c_double), ("nsim", C.c_int64)]
+
+
 class SubgTableDesc(C.Structure):
     """dcor_subg_table_desc (include/dcor.h): the shared table (p columns of n samples, ld apart), its
     per-column sub-Gaussian parameters (a HOST array of p doubles) and the call-wide settings."""
@@ -242,6 +250,8 @@ SIGNATURES = {
                                                  C.c_int64, _P, _P]),
     "dcor_hrs_private_table_launch": (C.c_int, [C.POINTER(HrsPrivateDesc), C.POINTER(HrsPairSegment),
                                                 C.c_int64, _P, _P, _P]),
+    "dcor_hrs_private_pairwise_launch": (C.c_int, [C.POINTER(HrsPrivateNaDesc), C.POINTER(HrsPairSegment),
+                                                   C.c_int64, _P, _P, _P]),
     "dcor_subg_panel_launch": (C.c_int, [C.POINTER(SubgPanelDesc), C.POINTER(SubgSegment), C.c_int64,
                                          _P, _P]),
     "dcor_subg_table_launch": (C.c_int, [C.POINTER(SubgTableDesc), C.POINTER(SubgPairSegment), C.c_int64,

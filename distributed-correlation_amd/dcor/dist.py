@@ -317,3 +317,16 @@ def hrs_private_distributed(raw, bounds, segs, group=None, **kw):
     if kw.get("return_priv"):
         raise ValueError("hrs_private_distributed gathers the records only: return_priv=False")
     return _segments_distributed(lambda mine: hrs.private_segments(raw, bounds, mine, **kw), segs, 5, 6, group)
+
+
+def hrs_private_pairwise_distributed(raw, bounds, segs, group=None, **kw):
+    """dcor.hrs.private_pairwise_segments over G ranks, as hrs_private_distributed: each rank runs its
+    pieces of the flattened (segment, replicate) space in one native call and the records are
+    all-gathered in rank order.  A record depends only on (columns, masks, bounds, budgets, seed_std,
+    eps, seeds, replicate), so the [sum(reps), 6] result, identical on all ranks, equals one process's
+    private_pairwise_segments(raw, bounds, segs) byte for byte.  return_priv is not gathered."""
+    from . import hrs
+    if kw.get("return_priv"):
+        raise ValueError("hrs_private_pairwise_distributed gathers the records only: return_priv=False")
+    return _segments_distributed(lambda mine: hrs.private_pairwise_segments(raw, bounds, mine, **kw), segs, 5, 6,
+                                 group)

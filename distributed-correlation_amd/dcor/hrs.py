@@ -629,3 +629,72 @@ def corr_matrix_sweep_pairwise(Z, lam, eps_grid=EPS_GRID, reps=R_PER_EPS, pairs=
     run = lambda segs: pairwise_segments(Z, lam, segs, nsim=nsim, alpha=alpha, delta=delta, valid=valid,
                                          stream=stream)
     return {**_corr_matrix_sweep(run, Z, eps_grid, reps, pairs), "n_pair": _n_pair(Z, valid)}
+
+
+# ------------- raw columns with gaps: the private standardisation per replicate, every pair on its own rows
+def private_pairwise_segments(raw, bounds, segs, eps_mean=EPS_MEAN, eps_m2=EPS_M2, seed_std=STD_SEED, nsim=2000,
+                              alpha=0.05, delta=None, valid=None, return_priv=False, stream=None):
+    """private_segments on a RAW (n, p) table with gaps, in one native call
+    (dcor_hrs_private_pairwise_launch): the reference's real-data pipeline, replicated.  In replicate r
+    column c is released by dp_sd from its own present rows (count n_c; real-data-sims.R:74) with the
+    unit Laplace pair dcor_draws_launch(0, seed_std, 17, r, 1, 2 p)[2 c : 2 c + 2], and a segment on
+    (col_x, col_y) runs on the n_ab rows present in both columns (:119-120, 187-189) with the geometry
+    and delta_clip = 1 / n_ab (delta=None) of that pair.  Its records equal pairwise_segments(Z_r, lam_r,
+    [the segment at rep_begin = r, reps = 1], valid=valid) byte for byte, (Z_r, lam_r) =
+    standardize_table(raw, bounds, lap = those draws, na="pairwise").  valid: the masks of
+    valid_mask(raw) by default (present = not NaN); the value of raw at a row its column's mask leaves
+    out is never used.  Every named pair needs 2 <= n_ab <= 65536.  -> float64 [sum(reps), 6] in segment
+    order, and with return_priv also [sum(reps), 6] (mean_x, sd_x, lam_x, mean_y, sd_y, lam_y)."""
+    import ctypes as C
+
+    from . import _lib
+    from ._segcall import pack_segments, run_segment_call
+    from .signpanel import _table
+    segs = list(segs)
+    F, n, p = _table(raw)
+    lo, hi = _bounds(bounds, p)
+    valid = valid_mask(F) if valid is None else np.ascontiguousarray(valid, dtype=np.uint64)
+    if valid.shape != (p, (n + 63) // 64):
+        raise ValueError(f"valid must be uint64 [{p}, {(n + 63) // 64}]")
+    for a, b, *_ in segs:
+        if not (0 <= int(a) < p and 0 <= int(b) < p):
+            raise ValueError(f"columns ({a}, {b}) outside [0, {p})")
+    arr, total = pack_segments(_lib.HrsPairSegment, segs, 6)
+    import torch
+    Dd = torch.as_tensor(F.reshape(-1, order="F"), device="cuda")   # the one upload
+    D = C.POINTER(C.c_double)
+    desc = _lib.HrsPrivateNaDesc(n=n, p=p, ld=n, D=Dd.data_ptr(), lo=lo.ctypes.data_as(D), hi=hi.ctypes.data_as(D),
+                                 valid=valid.ctypes.data_as(C.POINTER(C.c_uint64)), eps_mean=float(eps_mean),
+                                 eps_m2=float(eps_m2), seed_std=int(seed_std), alpha=float(alpha),
+                                 delta=float("nan") if delta is None else float(delta), nsim=int(nsim))
+    if not return_priv:
+        launch = lambda d, a, k, out, sp: _lib.lib.dcor_hrs_private_pairwise_launch(d, a, k, out, None, sp)
+        return run_segment_call(launch, desc, arr, len(segs), total, stream)
+    st = torch.cuda.current_stream() if stream is None else stream
+    with torch.cuda.stream(st):
+        priv = torch.empty((max(total, 1), 6), dtype=torch.float64, device="cuda")
+        launch = lambda d, a, k, out, sp: _lib.lib.dcor_hrs_private_pairwise_launch(
+            d, a, k, out, C.c_void_p(priv.data_ptr()), sp)
+        res = run_segment_call(launch, desc, arr, len(segs), total, st)   # waits for the stream
+        return res, priv[:total].cpu().numpy()
+
+
+def corr_matrix_private_pairwise(raw, bounds, eps, reps, pairs=None, eps_mean=EPS_MEAN, eps_m2=EPS_M2,
+                                 seed_std=STD_SEED, nsim=2000, alpha=0.05, delta=None, valid=None, stream=None):
+    """corr_matrix_private on a raw table with gaps (private_pairwise_segments): the same pairs, keys
+    and result, and "n_pair", the [p, p] integer matrix of the pairs' counts n_ab (the diagonal: n_c)."""
+    run = lambda segs: private_pairwise_segments(raw, bounds, segs, eps_mean=eps_mean, eps_m2=eps_m2,
+                                                 seed_std=seed_std, nsim=nsim, alpha=alpha, delta=delta,
+                                                 valid=valid, stream=stream)
+    return {**_corr_matrix(run, raw, eps, reps, pairs), "n_pair": _n_pair(raw, valid)}
+
+
+def corr_matrix_sweep_private_pairwise(raw, bounds, eps_grid=EPS_GRID, reps=R_PER_EPS, pairs=None,
+                                       eps_mean=EPS_MEAN, eps_m2=EPS_M2, seed_std=STD_SEED, nsim=2000, alpha=0.05,
+                                       delta=None, valid=None, stream=None):
+    """corr_matrix_sweep_private on a raw table with gaps (private_pairwise_segments): the same pairs,
+    keys and result, and "n_pair", the [p, p] integer matrix of the pairs' counts n_ab."""
+    run = lambda segs: private_pairwise_segments(raw, bounds, segs, eps_mean=eps_mean, eps_m2=eps_m2,
+                                                 seed_std=seed_std, nsim=nsim, alpha=alpha, delta=delta,
+                                                 valid=valid, stream=stream)
+    return {**_corr_matrix_sweep(run, raw, eps_grid, reps, pairs), "n_pair": _n_pair(raw, valid)}

@@ -609,6 +609,62 @@ int dcor_hrs_private_table_launch(const dcor_hrs_private_desc* t, const dcor_hrs
                                   int64_t nseg, dcor_rep_out* d_out, double* d_priv /* nullable */,
                                   void* stream);
 
+/* dcor_hrs_private_table_launch on a table with gaps: the reference's real-data pipeline as it runs
+ * on hrs_long_panel.rds, the private standardisation drawn per replicate AND every pair on its own
+ * pairwise-complete rows.  dp_sd drops a column's own NA (x <- x[!is.na(x)], real-data-sims.R:74), so
+ * a column's private mean and sd are released from the column's own count; correlation_NI_subG and
+ * ci_INT_subG then drop NA per pair (:119-120, :187-189) and take the geometry, delta_clip = 1 / n
+ * and lambda_receiver from the pair's count.  valid holds one presence mask per column, as in
+ * dcor_hrs_table_na_desc.
+ * Column release in replicate r: n_c = popcount of column c's mask over the rows below n; (mean_c,
+ * sd_c) = dcor_dp_sd on the column's present rows in row order, so the count is n_c and the scales
+ * are (hi - lo) / (n_c eps_mean) and (hi^2 - lo^2) / (n_c eps_m2); the two unit Laplace draws are
+ * those of Philox block (c, r, DCOR_SITE_STD, 0) under seed_std, dcor_hrs_private_table_launch's draw
+ * contract unchanged; lam_c = dcor_lambda_from_priv.  The release depends on (column, its mask, lo,
+ * hi, budgets, seed_std, r) only: never on the partner column, the partner's mask, eps or the
+ * segment.
+ * Pair: ok = valid[col_x] & valid[col_y], n_ab = popcount(ok); the samples are (clip(x_i, lo, hi) -
+ * mean) / den for i in ok, in row order, an IEEE division; the geometry, the Feistel split, delta = 1
+ * / n_ab when delta is NaN and every lambda-dependent constant are those of n_ab.
+ * Contract: replicate r of a segment equals, byte for byte, dcor_hrs_table_pairwise_launch at
+ * rep_begin = r, reps = 1 with the same masks, delta, seeds, eps, alpha and nsim on the table whose
+ * column c is dcor_standardize_dp(D[c], lo[c], hi[c], mean_c, sd_c, 1e-8) with lam[c] as above.  With
+ * every mask bit set and delta = 1 / n the call equals dcor_hrs_private_table_launch byte for byte,
+ * d_priv included.  The value of D at a row its column's mask leaves out is never read into any
+ * result (NaN, +-1e300 or anything else gives the same records).  A NaN at a present row of column c
+ * makes that column's sums NaN, and so every record and d_priv triple of every pair that names c;
+ * other pairs are untouched.  Records depend only on (columns, masks, lo, hi, budgets, seeds, eps,
+ * replicate), never on the segment split, the segment order or out_row.  d_priv: the private
+ * entry's layout, (mean_x, sd_x, lam_x, mean_y, sd_y, lam_y) at row out_row + j.
+ * Launches: one workgroup per column compacts its present rows in order (8 B per present row of
+ * stream-ordered scratch) and a second takes dcor_dp_sd's two means of that copy -- the sum is
+ * thread-strided over the index, so only the compacted column gives the helper's bits --; one
+ * workgroup per distinct ordered pair packs its rows clipped to the raw intervals; one streaming and
+ * one epilogue launch cover every pair and eps, the replicate's affine map applied at gather time.
+ * Checks, all on the host before anything is enqueued and before any device access (an invalid call
+ * returns its code and leaves d_out and d_priv untouched), the union of the two parents': 2 <= n <
+ * 2^31; non-null D, lo, hi, valid; every lo[c], hi[c] finite with lo[c] < hi[c]; eps_mean, eps_m2
+ * finite and > 0; delta > 0 or NaN; the segment and replicate-range checks of dcor_hrs_table_launch;
+ * every named pair 2 <= n_ab <= 65536, else DCOR_EINVAL with dcor_last_error naming the segment and
+ * n_ab; scratch bytes representable.  nseg == 0 or no replicates at all returns DCOR_OK with no
+ * device work.  Asynchronous on `stream`, no host synchronisation.  DCOR_HRS_WPE acts as in
+ * dcor_hrs_fused_launch.  D, lo, hi, valid and segs are borrowed for the call only (D until the
+ * call's work on `stream` has run). */
+typedef struct dcor_hrs_private_na_desc {   /* dcor_hrs_private_desc and the masks */
+  int64_t n, p, ld;         /* RAW columns, column c = D + c * ld (DEVICE) */
+  const double* D;
+  const double* lo;         /* HOST, [p]: raw clip interval of column c, finite, lo[c] < hi[c] */
+  const double* hi;
+  const uint64_t* valid;    /* HOST, [p][ceil(n / 64)], as dcor_hrs_table_na_desc */
+  double eps_mean, eps_m2;  /* > 0, finite */
+  uint64_t seed_std;        /* Philox key of the standardisation draws, call-wide */
+  double alpha, delta;      /* delta > 0, or NaN: 1 / n_ab per pair (real-data-sims.R:199) */
+  int64_t nsim;
+} dcor_hrs_private_na_desc;
+int dcor_hrs_private_pairwise_launch(const dcor_hrs_private_na_desc* t, const dcor_hrs_pair_segment* segs,
+                                     int64_t nseg, dcor_rep_out* d_out, double* d_priv /* nullable */,
+                                     void* stream);
+
 /* The sub-Gaussian estimators of the simulation (correlation_NI_subG + ci_INT_subG,
  * ver-cor-subG.R:25-108: contiguous batches, lambda_n / lambda_INT_n, any (eps1, eps2), either
  * sender) on the caller's own (X, Y), prepared once and shared by every replicate, with every noise
