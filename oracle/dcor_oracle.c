@@ -703,6 +703,9 @@ int orc_sim_rep(const void* cellp, int64_t rep, double out[6]) {
   if (n < 1 || !(c->eps1 > 0) || !(c->eps2 > 0)) return DCOR_EINVAL;
   if (orc_cell_check(c)) return DCOR_EINVAL;
   const int64_t nsim = c->nsim;
+  /* the cell contract of dcor_sim_launch (include/dcor.h: 1 <= nsim <= 2048), which R does not
+   * have: a cell the engine refuses has no reference records either */
+  if (nsim < 1 || nsim > 2048) return DCOR_EINVAL;
   const int subg = (c->family == DCOR_FAMILY_SUBG);
   double* X = (double*)malloc(sizeof(double) * (size_t)n);
   double* Y = (double*)malloc(sizeof(double) * (size_t)n);
